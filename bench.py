@@ -13,6 +13,13 @@ per-GPU work is fixed (weak scaling).  `value` = group-steps of all ranks ÷
 the max-over-ranks timed-region wall time.
 
 Outputs ONE JSON line on rank 0 (see DESIGN.md §Measurement for the byte model).
+
+A plain run settles, warms up, times `--steps` rounds and prints the line.
+`--full` adds what takes runs of its own: the per-kernel split and the
+dominant kernel's roofline (profiled rounds after the timed region), the other
+BASELINE configurations (`--also`), the CPU baselines, and for c5 the exchange
+share.  `--dump-outputs DIR` writes what the last timed round left for the
+caller (dump_outputs) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -233,6 +240,96 @@ def alg_bytes(c):
     return sum(BYTES[k] * c[k] for k in BYTES)
 
 
+# --dump-outputs: the sample is blocks of DUMP_BLOCK consecutive groups (every
+# replica of each), drawn with a fixed seed from the engine's groups, at most
+# DUMP_REPLICAS replicas in all, with at most the first DUMP_ROWS Messages and
+# ReadyToReads of the sample (block order, then replica order): 16384 groups x
+# 3 replicas of C4 are ~32 MB of float64 columns, and no workload passes 60 MB
+DUMP_BLOCK = 512
+DUMP_REPLICAS = 49152
+DUMP_ROWS = 200_000
+DUMP_SEED = 0xD0C5
+
+
+def _columns(a):
+    """A structured array as (column names, [n, columns] float64).  The 64-bit
+    digest is split into two exact 32-bit halves; every other field is a term,
+    an index, a count or a bit set well below 2**53 (or the all-ones sentinel,
+    which rounds the same way in every run)."""
+    import numpy as np
+    names, cols = [], []
+    for f in a.dtype.names:
+        sub = a.dtype[f].shape
+        v = a[f].reshape(len(a), sub[0] if sub else 1)
+        for j in range(v.shape[1]):
+            nm = f if v.shape[1] == 1 else f"{f}[{j}]"
+            if f == "digest":
+                names += [nm + "_hi", nm + "_lo"]
+                cols += [(v[:, j] >> np.uint64(32)).astype(np.float64),
+                         (v[:, j] & np.uint64(0xFFFFFFFF)).astype(np.float64)]
+            else:
+                names.append(nm)
+                cols.append(v[:, j].astype(np.float64))
+    return names, np.stack(cols, axis=1)
+
+
+def dump_outputs(eng, out_dir, counters, rank=0, ws=1):
+    """What the last timed round left for the caller, for a fixed sample of
+    replicas, as float64 .npy files in out_dir (columns.json names the columns):
+      replicas        the sampled replica numbers
+      updates         their Updates of the last round (rbe_get_updates)
+      views           their protocol state after it (rbe_get_views)
+      messages        the last round's Messages of the sample, in transport
+                      order, column 0 the sending replica (rbe_collect_outputs);
+                      the first DUMP_ROWS of them
+      ready_to_reads  its ReadyToReads, column 0 the replica; likewise
+      counters        the engine's counters over the timed rounds
+    The engine's configuration and seed are fixed by the arguments, so two
+    builds run with the same arguments dump comparable arrays."""
+    import numpy as np
+    from dragonboat_amd.engine import COUNTER_NAMES, UPDATE_DTYPE
+    os.makedirs(out_dir, exist_ok=True)
+    N, ng = eng.n_replicas, eng.n_groups
+    nb = -(-ng // DUMP_BLOCK)
+    blocks = np.sort(np.random.default_rng(DUMP_SEED).choice(
+        nb, size=min(nb, max(1, DUMP_REPLICAS // (DUMP_BLOCK * N))), replace=False))
+    eng.sync()
+    reps, ups, views, msgs, rtrs = [], [], [], [], []
+    for b in blocks:
+        g0, g1 = int(b) * DUMP_BLOCK, min(ng, (int(b) + 1) * DUMP_BLOCK)
+        first, count = g0 * N, (g1 - g0) * N
+        rep = np.arange(first, first + count, dtype=np.uint64)
+        reps.append(rep)
+        ups.append(np.frombuffer(bytes(eng.updates(first, count)), UPDATE_DTYPE))
+        views.append(eng.views_np(first, count).copy())
+        moff, m, roff, r = eng.collect_outputs(first, count)
+        msgs.append((np.repeat(rep, np.diff(moff).astype(np.int64)), m))
+        rtrs.append((np.repeat(rep, np.diff(roff).astype(np.int64)), r))
+    arrays, columns = {}, {}
+
+    def put(name, names, arr):
+        columns[name] = names
+        arrays[name] = np.ascontiguousarray(arr, dtype=np.float64)
+
+    put("replicas", ["replica"], np.concatenate(reps).astype(np.float64)[:, None])
+    put("updates", *_columns(np.concatenate(ups)))
+    put("views", *_columns(np.concatenate(views)))
+    for name, parts in (("messages", msgs), ("ready_to_reads", rtrs)):
+        names, body = _columns(np.concatenate([p[1] for p in parts]))
+        owner = np.concatenate([p[0] for p in parts]).astype(np.float64)[:, None]
+        put(name, ["replica"] + names, np.concatenate([owner, body], axis=1)[:DUMP_ROWS])
+    put("counters", list(COUNTER_NAMES),
+        np.array([[counters[k] for k in COUNTER_NAMES]], dtype=np.float64))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64_000_000:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the 64 MB bound")
+    sfx = f"_rank{rank}" if ws > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+    with open(os.path.join(out_dir, f"columns{sfx}.json"), "w") as f:
+        json.dump(columns, f, indent=1)
+
+
 def load_traffic(name, kernel, lib):
     """Measured HBM bytes per launch of `kernel` from the committed PMC summary
     (profiles/traffic_<workload>.json, written by scripts/pmc_traffic.py), only
@@ -365,36 +462,41 @@ def run_replica_mode(args, ws, rank, local, dist, dev, gloo_staged):
     c = eng.counters()
     nf, fo = eng.fault_summary()
     sent = (xch.bytes_sent - b0) if xch else 0
-    # exchange share, on separate rounds (the sync before each exchange would
-    # otherwise perturb the timed region)
-    xt = [0.0]
-    rounds(min(args.steps, 20), timed_xchg=xt)
-    xchg_ms = xt[0] * 1e3 / min(args.steps, 20)
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, c, rank, ws)
+    # --full: exchange share, on separate rounds (the sync before each exchange
+    # would otherwise perturb the timed region)
+    xchg_ms = 0.0
+    if args.full:
+        xt = [0.0]
+        rounds(min(args.steps, 20), timed_xchg=xt)
+        xchg_ms = xt[0] * 1e3 / min(args.steps, 20)
     red_dev = None if gloo_staged or ws == 1 else dev
     wall_max, (steps, committed, reads, faulty, sent_all, xms_sum) = reduce_results(
         dist if ws > 1 else None, wall, [c["steps"], c["committed"], c["reads_confirmed"], nf,
                                          sent, xchg_ms], device=red_dev)
-    xms_mean = xms_sum / ws
-    # kernel split: single profiled rounds, each followed by its exchange
-    prof_rounds = max(1, min(args.steps, args.prof_rounds))
-    eng.reset_counters()
-    kms = [0.0] * 4
-    for _ in range(prof_rounds):
-        if xch is not None:
-            xch.iso_sync()
-        for i, v in enumerate(eng.profile_rounds(1)):
-            kms[i] += v
-        if xch is not None:
-            xch.exchange()
-    kernels = []
-    for ki, name in enumerate(eng.kernel_names()):
-        if not name:
-            continue
-        b = alg_bytes(eng.kernel_counters(ki)) / prof_rounds
-        us = kms[ki] * 1e3 / prof_rounds
-        kernels.append({"kernel": name, "avg_us": us, "alg_bytes_per_launch": b,
-                        "achieved_gbs": (b / (us * 1e-6) / 1e9) if us > 0 else 0.0})
-    dom = max(kernels, key=lambda k: k["avg_us"])
+    xms_mean = xms_sum / ws if args.full else None
+    # --full: kernel split, single profiled rounds, each followed by its exchange
+    kernels, dom = [], None
+    if args.full:
+        prof_rounds = max(1, min(args.steps, args.prof_rounds))
+        eng.reset_counters()
+        kms = [0.0] * 4
+        for _ in range(prof_rounds):
+            if xch is not None:
+                xch.iso_sync()
+            for i, v in enumerate(eng.profile_rounds(1)):
+                kms[i] += v
+            if xch is not None:
+                xch.exchange()
+        for ki, name in enumerate(eng.kernel_names()):
+            if not name:
+                continue
+            b = alg_bytes(eng.kernel_counters(ki)) / prof_rounds
+            us = kms[ki] * 1e3 / prof_rounds
+            kernels.append({"kernel": name, "avg_us": us, "alg_bytes_per_launch": b,
+                            "achieved_gbs": (b / (us * 1e-6) / 1e9) if us > 0 else 0.0})
+        dom = max(kernels, key=lambda k: k["avg_us"])
     if rank == 0:
         out = {
             "metric": METRIC, "value": steps / wall_max, "unit": "group-steps/s",
@@ -421,13 +523,15 @@ def run_replica_mode(args, ws, rank, local, dist, dev, gloo_staged):
                          # fixed rounds whose records outgrew the chunks, repaired
                          # by a counted second pass (rank 0; never invalid)
                          "repaired_rounds": xch.repaired if xch is not None else 0},
-            "roofline": {"bound": "hbm", "achieved": dom["achieved_gbs"], "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": dom["achieved_gbs"] / HBM_PEAK_GBS,
-                         "traffic": None, "kernel": dom["kernel"],
-                         "alg_bytes_per_launch": dom["alg_bytes_per_launch"],
-                         "avg_launch_us": dom["avg_us"], "profiled_rounds": prof_rounds},
-            "round": {"kernels": kernels},
         }
+        if args.full:
+            out["roofline"] = {
+                "bound": "hbm", "achieved": dom["achieved_gbs"], "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": dom["achieved_gbs"] / HBM_PEAK_GBS,
+                "traffic": None, "kernel": dom["kernel"],
+                "alg_bytes_per_launch": dom["alg_bytes_per_launch"],
+                "avg_launch_us": dom["avg_us"], "profiled_rounds": prof_rounds}
+            out["round"] = {"kernels": kernels}
         print(json.dumps(out), flush=True)
     eng.close()
 
@@ -658,6 +762,8 @@ def run_host_driven(args, ws, rank, local, dist):
     nf, fo = eng.fault_summary()
     wall_max, (steps, committed, reads) = reduce_results(
         dist, wall, [c["steps"], c["committed"], c["reads_confirmed"]])
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, c, rank, ws)
     K = args.steps
     if rank == 0:
         print(json.dumps({
@@ -712,11 +818,20 @@ def main():
     ap.add_argument("--cfg", default="",
                     help="engine capacity overrides for A/B runs, e.g. maxm=4,ecap=16 "
                          "(recorded in the line's config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the per-kernel split and "
+                         "roofline (--prof-rounds), the --also workloads, the CPU baselines "
+                         "(unless --no-cpu-baseline), c5's exchange share")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the last step's outputs for a fixed "
+                         "sample of replicas to DIR/<name>.npy (float64; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: leave the CPU baselines out")
     ap.add_argument("--no-compact", action="store_true",
                     help="c5: allocate every group's planes on every rank")
     ap.add_argument("--prof-rounds", type=int, default=50,
-                    help="rounds profiled per kernel with HIP events after the timed region")
+                    help="--full: rounds profiled per kernel with HIP events after the timed "
+                         "region")
     ap.add_argument("--cpu-groups", type=int, default=0,
                     help="groups in the T-thread CPU sample (0 = per-workload default)")
     ap.add_argument("--cpu-rounds", type=int, default=100)
@@ -726,7 +841,8 @@ def main():
     ap.add_argument("--xchg-gloo", action="store_true",
                     help="c5 rehearsal: all ranks on cuda:0, exchange over gloo via host memory")
     ap.add_argument("--also", default="c2,c3",
-                    help="other workloads timed briefly in the same run (comma list, '' = none)")
+                    help="--full: other workloads timed briefly in the same run (comma list, "
+                         "'' = none)")
     ap.add_argument("--c4h-all-msgs", action="store_true",
                     help="c4h: read every message back too (rbe_collect_outputs)")
     ap.add_argument("--c4h-serial", action="store_true",
@@ -801,30 +917,34 @@ def main():
         dist if use_dist else None, wall,
         [c["steps"], c["committed"], c["reads_confirmed"], nf], device=red_dev)
 
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, c, rank, ws)
+
     # whole-round algorithmic bandwidth over the timed region (all kernels)
     round_bytes = alg_bytes(c) / args.steps
     round_gbs = round_bytes / ((ev_ms / 1e3) / args.steps) / 1e9
+    lib = lib_identity()
 
-    # per-kernel split: a further `prof_rounds` rounds, one at a time, each
-    # kernel launched with a start / stop HIP event pair its own dispatch
+    # --full, per-kernel split: a further `prof_rounds` rounds, one at a time,
+    # each kernel launched with a start / stop HIP event pair its own dispatch
     # stamps (hipExtLaunchKernel, on the engine stream: the kernel's execution
     # as rocprofv3 times it) and each kernel's own counters -> the dominant
     # kernel's roofline
-    prof_rounds = max(1, min(args.steps, args.prof_rounds))
-    eng.reset_counters()
-    kms = eng.profile_rounds(prof_rounds)
-    kernels = []
-    for ki, name in enumerate(eng.kernel_names()):
-        if not name:
-            continue
-        kc = eng.kernel_counters(ki)
-        b = alg_bytes(kc) / prof_rounds
-        us = kms[ki] * 1e3 / prof_rounds
-        kernels.append({"kernel": name, "avg_us": us, "alg_bytes_per_launch": b,
-                        "achieved_gbs": (b / (us * 1e-6) / 1e9) if us > 0 else 0.0})
-    dom = max(kernels, key=lambda k: k["avg_us"])
-    lib = lib_identity()
-    traffic, traffic_src = load_traffic(args.workload, dom["kernel"], lib)
+    if args.full:
+        prof_rounds = max(1, min(args.steps, args.prof_rounds))
+        eng.reset_counters()
+        kms = eng.profile_rounds(prof_rounds)
+        kernels = []
+        for ki, name in enumerate(eng.kernel_names()):
+            if not name:
+                continue
+            kc = eng.kernel_counters(ki)
+            b = alg_bytes(kc) / prof_rounds
+            us = kms[ki] * 1e3 / prof_rounds
+            kernels.append({"kernel": name, "avg_us": us, "alg_bytes_per_launch": b,
+                            "achieved_gbs": (b / (us * 1e-6) / 1e9) if us > 0 else 0.0})
+        dom = max(kernels, key=lambda k: k["avg_us"])
+        traffic, traffic_src = load_traffic(args.workload, dom["kernel"], lib)
 
     if rank == 0:
         out = {
@@ -855,7 +975,15 @@ def main():
             "read_confirmations_per_s": reads / wall_max,
             "faulty_replicas": int(faulty),
             "fault_bits_rank0": fo,
-            "roofline": {
+            "round": {
+                "alg_bytes_per_round": round_bytes,
+                "achieved_gbs": round_gbs,
+                "frac": round_gbs / HBM_PEAK_GBS,
+                "event_ms_per_round": ev_ms / args.steps,
+            },
+        }
+        if args.full:
+            out["roofline"] = {
                 "bound": "hbm",
                 "achieved": dom["achieved_gbs"],
                 "peak": HBM_PEAK_GBS,
@@ -867,26 +995,19 @@ def main():
                 "alg_bytes_per_launch": dom["alg_bytes_per_launch"],
                 "avg_launch_us": dom["avg_us"],
                 "profiled_rounds": prof_rounds,
-            },
-            "round": {
-                "alg_bytes_per_round": round_bytes,
-                "achieved_gbs": round_gbs,
-                "frac": round_gbs / HBM_PEAK_GBS,
-                "event_ms_per_round": ev_ms / args.steps,
-                "kernels": kernels,
-            },
-        }
+            }
+            out["round"]["kernels"] = kernels
         out["library"] = lib
         # the other single-GPU BASELINE configurations, timed in the same run
         # (parity cases elsewhere; here only their rate and kernel split)
-        if ws == 1 and args.also:
+        if args.full and ws == 1 and args.also:
             out["workloads"] = {}
             for name in [x for x in args.also.split(",") if x and x != args.workload]:
                 try:
                     out["workloads"][name] = side_line(name, local, 50, 20)
                 except Exception as ex:  # a side line must not hide the main one
                     out["workloads"][name] = {"error": repr(ex)}
-        if not args.no_cpu_baseline and ws == 1:
+        if args.full and not args.no_cpu_baseline and ws == 1:
             try:
                 ng = int(kw["n_groups"])
                 g_t = args.cpu_groups or min(ng, CPU_SAMPLE[args.workload][0])

@@ -1,8 +1,9 @@
 #!/bin/bash
 # One GPU-box runner for every measurement of a round (replaces the per-call
 # scripts of earlier rounds):
-#   gpurun -- bash scripts/gpu_run.sh OUT STEP [STEP ...]
-# OUT is a directory under gpurun_out/; the steps run in order, each under its
+#   bash scripts/gpu_run.sh OUT STEP [STEP ...]
+# OUT is a directory under $BENCH_OUT (default bench_out/, under the
+# repository root); the steps run in order, each under its
 # own time limit, and the first failure ends the call:
 #   smoke      __graft_entry__.smoke()
 #   spill      tests/test_gpu_spill.py (the spill tiers on the HIP engine)
@@ -14,7 +15,9 @@
 #   pmc        HBM traffic counters of the default bench (scripts/pmc_traffic.sh)
 set -e
 cd "$GRAFT_REPO_ROOT"
-O=gpurun_out/$1
+R=$PWD
+export BENCH_OUT=${BENCH_OUT:-bench_out}
+O=$BENCH_OUT/$1
 shift
 mkdir -p "$O"
 export TMPDIR=/tmp
@@ -35,16 +38,16 @@ for step in "$@"; do
         { grep -E "FAILED|Error" "$O/gpu_tests.log" | head -20; tail -30 "$O/gpu_tests.log"; exit 1; }
       tail -1 "$O/gpu_tests.log" ;;
     bench)
-      timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > "$O/bench_driver20.json" \
+      timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 > "$O/bench_driver20.json" \
         2> "$O/bench_driver20.err"
       python3 scripts/summarize_bench.py "$O/bench_driver20.json" driver20
-      timeout -k 10 300 python -u bench.py --no-cpu-baseline --also "" > "$O/bench_default.json" \
+      timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --also "" > "$O/bench_default.json" \
         2> "$O/bench_default.err"
       python3 scripts/summarize_bench.py "$O/bench_default.json" default ;;
     prof)
-      (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$O/prof" \
-        -o run --output-format csv -- python3 "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --also "" \
-        > "$GRAFT_REPO_ROOT/$O/bench_prof.json" 2> "$GRAFT_REPO_ROOT/$O/bench_prof.err") ;;
+      (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$R/$O/prof" \
+        -o run --output-format csv -- python3 "$R/bench.py" --full --no-cpu-baseline --also "" \
+        > "$R/$O/bench_prof.json" 2> "$R/$O/bench_prof.err") ;;
     c4h)
       timeout -k 10 400 python -u bench.py --workload c4h --steps 50 --warmup 5 --no-cpu-baseline \
         > "$O/bench_c4h.json" 2> "$O/bench_c4h.err"
@@ -56,7 +59,7 @@ for step in "$@"; do
       for mode in "" "--xchg-fixed"; do
         tag=${mode:+_fixed}
         timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-          --master-addr 127.0.0.1 --master-port 29533 bench.py --workload c5 --xchg-gloo $mode \
+          --master-addr 127.0.0.1 --master-port 29533 bench.py --full --workload c5 --xchg-gloo $mode \
           --groups ${C5_GROUPS:-100000} --steps 30 --warmup 5 --prof-rounds 10 \
           > "$O/bench_c5$tag.json" 2> "$O/bench_c5$tag.err" || { tail -30 "$O/bench_c5$tag.err"; exit 1; }
         python3 scripts/summarize_bench.py "$O/bench_c5$tag.json" "c5$tag"

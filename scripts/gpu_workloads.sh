@@ -5,12 +5,13 @@
 # own limit; the first failure ends the call.
 set -e
 cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
+export BENCH_OUT=${BENCH_OUT:-bench_out}
+mkdir -p "$BENCH_OUT"
 export TMPDIR=/tmp
 S=$(date +%s)
 for W in ${WORKLOADS:-c2 c3}; do
-  timeout -k 10 400 python -u bench.py --workload $W --steps ${STEPS:-50} > gpurun_out/bench_$W.json 2> gpurun_out/bench_$W.err
+  timeout -k 10 400 python -u bench.py --full --workload $W --steps ${STEPS:-50} > $BENCH_OUT/bench_$W.json 2> $BENCH_OUT/bench_$W.err
   echo "bench $W ok $(( $(date +%s) - S ))s"
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$W -o run --output-format csv -- python3 bench.py --workload $W --steps ${STEPS:-50} --no-cpu-baseline > gpurun_out/prof_$W.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $BENCH_OUT/prof_$W -o run --output-format csv -- python3 bench.py --full --workload $W --steps ${STEPS:-50} --no-cpu-baseline > $BENCH_OUT/prof_$W.log 2>&1
   echo "rocprof $W ok $(( $(date +%s) - S ))s"
 done

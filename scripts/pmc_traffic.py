@@ -84,7 +84,8 @@ def main():
         res["bytes_per_launch"][k] = fetch.get(k, 0.0) + write.get(k, 0.0)
         res["bytes_per_launch_fetch_x2"][k] = 2.0 * fetch.get(k, 0.0) + write.get(k, 0.0)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    out = os.path.join(ROOT, "gpurun_out", f"traffic_{w}.json")
+    # beside the counter directories (scripts/pmc_traffic.sh: $BENCH_OUT)
+    out = os.path.join(os.path.dirname(os.path.abspath(fdir)), f"traffic_{w}.json")
     with open(out, "w") as f:
         json.dump(res, f, indent=1)
     for k, v in sorted(res["bytes_per_launch"].items()):

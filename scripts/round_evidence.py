@@ -5,7 +5,7 @@ averages the LAST `window` dispatches of each round kernel — the bench's timed
 and profiled rounds, not its settle and warmup — next to the bench's own
 HIP-event split of the same rounds, with the ratio of the two.
 
-    python3 scripts/round_evidence.py gpurun_out/r06x profiles/r06_final [window]
+    python3 scripts/round_evidence.py bench_out/r06x profiles/r06_final [window]
 
 window defaults to the bench's steps + prof_rounds (read from its JSON line)."""
 import csv
@@ -76,7 +76,7 @@ hip0 = {k["kernel"]: k["avg_us"] for k in plain["round"]["kernels"]} if plain el
 if plain:
     shutil.copy(plain_p, os.path.join(dst, "bench_default.json"))
 lines = [f"# {os.path.basename(dst)}: steady-state round kernels", "",
-         f"Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --also \"\"` "
+         f"Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --also \"\"` "
          f"(C4, {b['steps']} timed + {b['roofline'].get('profiled_rounds', 0)} profiled rounds; "
          f"library {b.get('library', {}).get('sha256_16', '?')}).", "",
          f"rocprofv3 averages over the LAST {window} dispatches of each round kernel (the timed and "

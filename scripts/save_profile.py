@@ -1,4 +1,4 @@
-"""Copy a GPU pass's evidence from gpurun_out/ into profiles/<name>/ with a
+"""Copy a GPU pass's evidence from $BENCH_OUT (default bench_out/) into profiles/<name>/ with a
 summary of the timed window (the last STEPS dispatches of each kernel in the
 rocprofv3 kernel trace, which are the bench's timed rounds)."""
 import csv
@@ -11,14 +11,14 @@ from collections import defaultdict
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 name = sys.argv[1]
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
-# optional workload: take gpurun_out/bench_<w>.json and gpurun_out/prof_<w>/
+# optional workload: take bench_<w>.json and prof_<w>/ of that directory
 # (scripts/gpu_workloads.sh) instead of bench.json and prof/
 wl = sys.argv[3] if len(sys.argv) > 3 else None
 bench_name = f"bench_{wl}.json" if wl else "bench.json"
 prof_dir = f"prof_{wl}" if wl else "prof"
-cmd = f"python3 bench.py --workload {wl} --steps {steps} --no-cpu-baseline" if wl else \
-    "python3 bench.py --no-cpu-baseline"
-src = os.path.join(ROOT, "gpurun_out")
+cmd = f"python3 bench.py --full --workload {wl} --steps {steps} --no-cpu-baseline" if wl else \
+    "python3 bench.py --full --no-cpu-baseline"
+src = os.path.join(ROOT, os.environ.get("BENCH_OUT", "bench_out"))
 dst = os.path.join(ROOT, "profiles", name)
 os.makedirs(dst, exist_ok=True)
 for f in [bench_name, "gpu_tests.log", "smoke.log", "traffic_c4.json", "traffic_c2m.json"]:
