@@ -553,6 +553,62 @@ __global__ __launch_bounds__(kBlock) void k_ms_gather(Planes P, const u64* repli
   ms[i] = pack_ms(c.members & MB_REMOVED, x & 0xFFu, x >> 8);
 }
 
+// Demotion into the cold log's host tier (rbe_spill.h), after a round's
+// kernels and only with cfg.host_pool_bytes.  The plan: a fixed grid whose
+// lanes stride over the replicas, so a pass with nothing to do (at most half
+// the pool in use) is one small launch whose lanes return at their first load.
+static constexpr unsigned kPlanGrid = 1024;
+__global__ __launch_bounds__(kBlock) void k_cold_demote_plan(Planes P, Params C, RoundArg ra,
+                                                             ColdMove* mv, u32 mv_cap) {
+  const u32 par = clk_of(ra).round & 1u;
+  const u64 t0 = (u64)blockIdx.x * kBlock + threadIdx.x;
+  // One thread's housekeeping, while the other blocks already run: the other
+  // parity's move counter (its list was carried out after the last round) and
+  // the free-id ring's front with the bump counter.  Safe because nothing else
+  // in this kernel reads or writes those words: the plan counts moves in
+  // mv_n[par] and allocates host pages only.
+  if (t0 == 0) {
+    P.sctl->mv_n[par ^ 1u] = 0;
+    pool_fa_settle(P.sctl, C.pool_pages);
+  }
+  if (__hip_atomic_load(&P.sctl->live, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <=
+      C.pool_pages / 2)
+    return;
+  for (u64 r = t0; r < C.n_rep; r += (u64)gridDim.x * kBlock) {
+    ColdRef cr = P.cold[r];
+    if (!cr.head || cr.head == cr.tail) continue;
+    const u32 head = cr.head;
+    cold_demote_plan(P, C, cr, P.core[r].committed, par, mv, mv_cap);
+    if (cr.head != head) P.cold[r] = cr;
+  }
+}
+// The copy: a fixed grid whose waves stride over the planned moves, a lane
+// per entry (32 B as two 16-B accesses: a page is 2 KiB, coalesced), then one
+// lane gives the HBM page's id to the free-id ring
+static constexpr unsigned kDemoteGrid = 256;
+__global__ __launch_bounds__(kBlock) void k_cold_demote_copy(Planes P, RoundArg ra,
+                                                             const ColdMove* mv, u32 mv_cap,
+                                                             u32 host_pages) {
+  const u32 par = clk_of(ra).round & 1u;
+  const u32 n = cold_move_count(P.sctl, par, mv_cap);
+  const u32 first = P.sctl->hpool_first;
+  Ent* hpool = P.sctl->hpool;
+  const u32 lane = threadIdx.x & 63u;
+  const u32 w0 = (blockIdx.x * kBlock + threadIdx.x) >> 6, nw = gridDim.x * (kBlock >> 6);
+  for (u32 i = w0; i < n; i += nw) {
+    const ColdMove x = mv[i];
+    // (a null move; the range checks hold for every move the plan lists)
+    if (!x.dst || x.src >= first || x.dst - first >= host_pages) continue;
+    const uint4* src = (const uint4*)&P.pool[(u64)x.src * kPageEnts + lane];
+    uint4* dst = (uint4*)&hpool[(u64)(x.dst - first) * kPageEnts + lane];
+    const uint4 a = src[0], b = src[1];
+    dst[0] = a;
+    dst[1] = b;
+    if (lane == 0) cold_demote_done(P, x);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) cold_demote_account(P.sctl);
+}
+
 __global__ void k_advance(u32* clk, u32 k) {
   clk[0] += k;
   clk[1] += k;
@@ -724,6 +780,12 @@ struct rbe_engine {
   u64 out_dev_bytes = 0;
   u8* gat_dev = nullptr;  // rbe_get_entries' gather buffer (k_log_gather)
   u64 gat_dev_bytes = 0;
+  // the cold log's host tier (cfg.host_pool_bytes): the arena behind
+  // SpillCtl::hpool, and the demotion's move list (k_cold_demote_plan)
+  Ent* hpool_host = nullptr;
+  SpillCtl tier_init;  // the source of the tier constants' upload (rbe_create)
+  ColdMove* cmove = nullptr;
+  u32 cmove_cap = 0;
   u8* out_host = nullptr;
   u64 out_host_bytes = 0;
   // replica mode with the isolation schedule: every rank's leader bits, ORed
@@ -806,6 +868,12 @@ static int grow(u8** p, u64* have, u64 need, bool pinned);
 static int host_list(rbe_engine* e, u32 par, u64 li, u32 w, const Msg* pl, std::vector<Msg>& out);
 
 static constexpr int kPlaneAllocs = 30;
+// entries of the free-id ring: the power of two at or above pool_pages
+static u64 fa_ring_size(u32 pool_pages) {
+  u64 n = 64;
+  while (n < pool_pages) n <<= 1;
+  return n;
+}
 static u64 bytes_of(const Params& C, u64* parts) {
   const u64 N = C.n, G = C.n_groups, R = C.n_rep;
   u64 p[kPlaneAllocs] = {
@@ -837,7 +905,9 @@ static u64 bytes_of(const Params& C, u64* parts) {
       // spill tiers (rbe_spill.h): pool records, pool page links, cold-log refs,
       // the round spill heap (both parities), the allocation words
       (u64)C.pool_pages * kPageEnts * sizeof(Ent),
-      (u64)C.pool_pages * sizeof(PoolMeta),
+      // (both page tiers; with a host tier the free-id ring behind them, SpillCtl::fa)
+      ((u64)C.pool_pages + C.host_pages) * sizeof(PoolMeta) +
+          (C.host_pages ? fa_ring_size(C.pool_pages) * sizeof(u32) : 0),
       R * sizeof(ColdRef),
       2 * C.spill_units * 16,
       sizeof(SpillCtl),
@@ -958,11 +1028,20 @@ static int d2h(rbe_engine* e, T* dst, const T* src, u64 n) {
 
 static int launch_step(rbe_engine* e, RoundArg ra,
                        hipEvent_t* ev = nullptr) {
-  return dispatch_n(e->C.n, [&](auto NN) {
+  const int rc = dispatch_n(e->C.n, [&](auto NN) {
     constexpr int N = decltype(NN)::value;
     return e->C.trace ? launch_round<N, true>(e->P, e->C, e->L, e->stream, e->mode, ra, ev)
                       : launch_round<N, false>(e->P, e->C, e->L, e->stream, e->mode, ra, ev);
   });
+  if (rc || !e->C.host_pages) return rc;
+  // the cold log's host tier: the round's demotion, in line after its kernels
+  // (no new branch, so a K-round graph captures the two like the rest)
+  const unsigned gp = std::min(grid_for(e->C.n_rep), kPlanGrid);
+  hipLaunchKernelGGL(k_cold_demote_plan, dim3(gp), dim3(kBlock), 0, e->stream,
+                     e->P, e->C, ra, e->cmove, e->cmove_cap);
+  hipLaunchKernelGGL(k_cold_demote_copy, dim3(kDemoteGrid), dim3(kBlock), 0, e->stream, e->P, ra,
+                     (const ColdMove*)e->cmove, e->cmove_cap, e->C.host_pages);
+  return hipGetLastError() == hipSuccess ? RBE_OK : RBE_E_HIP;
 }
 
 // Sum the counter stripes of one kernel section (ks >= 0) or of all (ks < 0).
@@ -1035,6 +1114,10 @@ struct SnapLogDev {
     return m;
   }
   void page(u32 p, Ent* out) {
+    if (e->C.host_pages && p >= e->C.pool_pages) {  // (the stream was synchronised: read in place)
+      memcpy(out, e->hpool_host + (u64)(p - e->C.pool_pages) * kPageEnts, kPageEnts * sizeof(Ent));
+      return;
+    }
     if (hipMemcpy(out, e->P.pool + (u64)p * kPageEnts, kPageEnts * sizeof(Ent),
                   hipMemcpyDeviceToHost))
       rc = RBE_E_HIP;
@@ -1179,6 +1262,9 @@ int rbe_import_groups(rbe_engine* e, const void* buf, uint64_t bytes, uint32_t f
     e->tclk = h.tclk;
     const u32 clk[2] = {e->round, e->tclk};
     HIP_OK(hipMemcpyAsync(e->d_clk, clk, sizeof(clk), hipMemcpyHostToDevice, e->stream));
+    // (the round's parity may repeat the last one's: no demotion list is pending)
+    if (e->C.host_pages)
+      HIP_OK(hipMemsetAsync(e->P.sctl->mv_n, 0, sizeof(e->P.sctl->mv_n), e->stream));
   }
   // the awake lists and the sleeping totals restart from the scan
   HIP_OK(hipMemsetAsync(e->L.al_cnt, 0, 2 * e->L.al_nblk * sizeof(u32), e->stream));
@@ -1214,6 +1300,8 @@ int rbe_destroy(rbe_engine* e) {
   if (e->in_dev) HIP_IGNORE(hipFree(e->in_dev));
   if (e->out_dev) HIP_IGNORE(hipFree(e->out_dev));
   if (e->gat_dev) HIP_IGNORE(hipFree(e->gat_dev));
+  if (e->hpool_host) HIP_IGNORE(hipHostFree(e->hpool_host));
+  if (e->cmove) HIP_IGNORE(hipFree(e->cmove));
   if (e->out_host) HIP_IGNORE(hipHostFree(e->out_host));
   if (e->upd_dev) HIP_IGNORE(hipFree(e->upd_dev));
   if (e->ing_dev) HIP_IGNORE(hipFree(e->ing_dev));
@@ -1252,7 +1340,9 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
       const u64 pages = std::min<u64>(fr / 8, 32ull << 30) / (kPageEnts * sizeof(Ent));
-      if (pages > C.pool_pages) C.pool_pages = (u32)std::min<u64>(pages, 0xFFFFFFF0ull);
+      // (page ids are u32 across both tiers: spill_sizes' bound with a host tier)
+      const u64 cap = C.host_pages ? 0xFFFFFFEFull - C.host_pages : 0xFFFFFFF0ull;
+      if (pages > C.pool_pages) C.pool_pages = (u32)std::min<u64>(pages, cap);
     }
   }
   rbe_engine* e = new (std::nothrow) rbe_engine();
@@ -1323,6 +1413,35 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
   P.spill[0] = (u8*)ptrs[28];
   P.spill[1] = P.spill[0] + C.spill_units * 16;
   P.sctl = (SpillCtl*)ptrs[29];
+  if (C.host_pages) {
+    // the cold log's host tier: pinned, device-mapped pages the kernels read
+    // in place, and the demotion's move list (at most every HBM page in a pass)
+    const u64 hb = (u64)C.host_pages * kPageEnts * sizeof(Ent);
+    e->cmove_cap = (u32)std::min<u64>(std::max<u64>(C.pool_pages, 64), 1u << 20);
+    void* dp = nullptr;
+    if (hipHostMalloc((void**)&e->hpool_host, hb, hipHostMallocMapped) != hipSuccess ||
+        !e->hpool_host || hipHostGetDevicePointer(&dp, e->hpool_host, 0) != hipSuccess || !dp ||
+        hipMalloc((void**)&e->cmove, (u64)e->cmove_cap * sizeof(ColdMove)) != hipSuccess) {
+      rbe_destroy(e);
+      return RBE_E_NOMEM;
+    }
+    HIP_IGNORE(hipMemsetAsync(e->cmove, 0, (u64)e->cmove_cap * sizeof(ColdMove), e->stream));
+    // the tier's constants live in SpillCtl (rbe_types.h): the words from
+    // `hpool` to `fa_n`, uploaded after the planes' zero fill on the same stream
+    SpillCtl& t = e->tier_init;
+    memset(&t, 0, sizeof(t));
+    t.hpool = (Ent*)dp;
+    t.fa = (u32*)(P.pmeta + ((u64)C.pool_pages + C.host_pages));
+    t.hpool_first = C.pool_pages;
+    t.hpool_pages = C.host_pages;
+    t.fa_mask = (u32)(fa_ring_size(C.pool_pages) - 1);
+    const size_t o0 = offsetof(SpillCtl, hpool), o1 = offsetof(SpillCtl, pad1);
+    if (hipMemcpyAsync((u8*)P.sctl + o0, (const u8*)&t + o0, o1 - o0, hipMemcpyHostToDevice,
+                       e->stream) != hipSuccess) {
+      rbe_destroy(e);
+      return RBE_E_HIP;
+    }
+  }
   // page 0 is the null page: the bump counter starts at 1
   HIP_IGNORE(hipMemsetD32Async((hipDeviceptr_t)&P.sctl->bump, 1, 1, e->stream));
   P.node_ids = nullptr;  // slot s is node s + 1 until rbe_set_node_ids
@@ -2903,6 +3022,19 @@ int rbe_spill_stats(rbe_engine* e, uint64_t* out) {
   out[2] = std::max(s.peak[0], s.peak[1]) * 16;
   out[3] = e->C.spill_units * 16;
   out[4] = s.oom;
+  return RBE_OK;
+}
+
+int rbe_cold_tier_stats(rbe_engine* e, uint64_t* out) {
+  if (!e || !out) return RBE_E_INVALID;
+  HIP_OK(hipSetDevice(e->device));
+  SpillCtl s;
+  HIP_OK(hipMemcpyAsync(&s, e->P.sctl, sizeof(s), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  out[0] = s.hlive;
+  out[1] = e->C.host_pages;
+  out[2] = s.demoted;
+  out[3] = s.passes;
   return RBE_OK;
 }
 

@@ -45,10 +45,12 @@ inline auto with_n(u32 n, F&& f) -> decltype(f(std::integral_constant<int, 1>())
 }
 
 // The spill tiers' sizes (rbe_spill.h): cfg.pool_bytes of page pool (0 = 8
-// KiB per replica, at least 64 MiB and at most 32 GiB: four pages, 256
-// entries of cold log, per replica on average) and cfg.spill_bytes of round
-// spill heap per round parity (0 = 128 B per replica, at least 16 MiB, at most
-// 4 GiB).  Shared with the test-only host build (tests/soa_cpu).
+// KiB per replica, at least 64 MiB and at most 32 GiB, which rbe_create raises
+// to an eighth of the device's free HBM, at most 32 GiB, when that is more:
+// include/rbe.h), cfg.host_pool_bytes of host tier under it (0 = none) and
+// cfg.spill_bytes of round spill heap per round parity (0 = 128 B per replica,
+// at least 16 MiB, at most 4 GiB).  Page ids are u32 across both page tiers.
+// Shared with the test-only host build (tests/soa_cpu), which has no host tier.
 inline int spill_sizes(const rbe_config* cfg, Params* C) {
   const u64 R = C->n_rep, page = (u64)kPageEnts * sizeof(Ent);
   u64 pb = cfg->pool_bytes;
@@ -56,6 +58,10 @@ inline int spill_sizes(const rbe_config* cfg, Params* C) {
   u64 pages = pb / page;
   if (pages < 2 || pages > 0xFFFFFFF0ull) return RBE_E_INVALID;
   C->pool_pages = (u32)pages;
+  const u64 hp = cfg->host_pool_bytes / page;
+  if (cfg->host_pool_bytes && (hp == 0 || C->rep_world > 1)) return RBE_E_INVALID;
+  if (hp > 0xFFFFFFF0ull || pages + hp >= 0xFFFFFFF0ull) return RBE_E_INVALID;
+  C->host_pages = (u32)hp;
   u64 sb = cfg->spill_bytes;
   const u64 W = C->rep_world > 1 ? C->rep_world : 1;  // (a share per rank: spill_alloc)
   if (!sb) sb = std::min(std::min(std::max(R * 128ull, 16ull << 20), 4ull << 30) * W, 0xFFFFFFF0ull * 16);

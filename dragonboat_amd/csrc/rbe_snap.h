@@ -262,7 +262,11 @@ RBE_HD u64 snap_log_rebuild(const Planes& P, const Params& C, u64 r, const u8* r
   cr.tail_pn = 0;
   for (u32 i = 0; i < h.n_pages; i++, at += sizeof(SnapPage)) {
     const SnapPage* sp = (const SnapPage*)(rec + at);
-    const u32 p = pool_alloc(P, C, par);
+    // with a host tier every page but the tail goes there (an HBM page when
+    // it is full), so a tiered engine takes back its own export whatever the
+    // size of its HBM pool; the tail stays where the steps append to it
+    u32 p = P.sctl->hpool_first && i + 1 < h.n_pages ? host_alloc(P, C) : 0u;
+    if (!p) p = pool_alloc(P, C, par);
     if (!p) {
       P.cold[r] = cr;
       *fault = F_NOMEM;
@@ -300,7 +304,7 @@ RBE_HD u64 snap_log_rebuild(const Planes& P, const Params& C, u64 r, const u8* r
         else x.head = p;
         x.tail = p;
       }
-      *(ReadReq*)pool_ent(P, x.tail, i % kPageEnts) = *(const ReadReq*)(rec + at);
+      *(ReadReq*)&P.pool[(u64)x.tail * kPageEnts + i % kPageEnts] = *(const ReadReq*)(rec + at);
       x.n++;
     }
     rq_ext_store(P, C, r, x);

@@ -76,10 +76,29 @@ RBE_HD void sp_atomic_max_u64(u64* p, u64 v) {
 }
 
 // ---------------------------------------------------------------- page pool
+// A record of a page of either tier.  A page of the host tier (id at or past
+// SpillCtl::hpool_first, when there is one) is read and written in place over
+// the host link; only cold log pages below a chain's tail are ever there.
+// (The tier's constants are loaded from SpillCtl, on these rare paths only.)
+template <class PL>
+RBE_HD bool pool_is_host(const PL& P, u32 page) {
+  const u32 first = P.sctl->hpool_first;
+  return first && page >= first;
+}
 template <class PL>
 RBE_HD Ent* pool_ent(const PL& P, u32 page, u32 slot) {
+  const u32 first = P.sctl->hpool_first;
+  if (first && page >= first) return &P.sctl->hpool[(u64)(page - first) * kPageEnts + slot];
   return &P.pool[(u64)page * kPageEnts + slot];
 }
+// With a host tier the HBM pages demotion frees do not go onto a free stack:
+// their ids go into a ring (SpillCtl::fa) and the bump counter, once it has
+// handed out every page of the pool, runs on into the ring's entries.  So the
+// allocation of a tiered pool is the one atomicAdd it always was, a freed page
+// serves a round of either parity, and the code sits in what was the
+// exhausted branch.  (A CAS stack serialises the lanes of a round in which
+// every log crosses a page boundary on one word, retries growing with their
+// square, and serves one round parity only.)
 // a page for a step of round parity `par`; 0 when the pool is exhausted
 template <class PL, class PA>
 RBE_HD u32 pool_alloc(const PL& P, const PA& C, u32 par) {
@@ -103,6 +122,12 @@ RBE_HD u32 pool_alloc(const PL& P, const PA& C, u32 par) {
   }
   const u32 p = sp_atomic_add_u32(&s->bump, 1u);
   if (p >= C.pool_pages) {
+    // (fa_base and fa_n do not move while a kernel allocates)
+    const u32 i = p - C.pool_pages;
+    if (s->hpool_first && i < s->fa_n) {
+      sp_atomic_add_u32(&s->live, 1u);
+      return s->fa[(s->fa_base + i) & s->fa_mask];
+    }
     sp_atomic_or_u32(&s->oom, 1u);
     return 0;
   }
@@ -111,8 +136,11 @@ RBE_HD u32 pool_alloc(const PL& P, const PA& C, u32 par) {
 }
 template <class PL>
 RBE_HD void pool_free(const PL& P, u32 par, u32 page) {
-  sp_atomic_add_u32(&P.sctl->live, ~0u);  // - 1
-  u32* fh = &P.sctl->free_head[par];
+  // a host page goes to the host tier's own stack, whatever the parity: the
+  // round kernels only push it, the demotion plan and an import only pop it
+  const bool host = pool_is_host(P, page);
+  sp_atomic_add_u32(host ? &P.sctl->hlive : &P.sctl->live, ~0u);  // - 1
+  u32* fh = host ? &P.sctl->hfree : &P.sctl->free_head[par];
 #if defined(__HIP_DEVICE_COMPILE__)
   u32 h = __hip_atomic_load(fh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   for (;;) {
@@ -164,6 +192,10 @@ template <class PL, class PA>
 RBE_HD bool cold_put(const PL& P, const PA& C, ColdRef& cr, u64 idx, const Ent& e, u32 par) {
   const u64 pn = idx / kPageEnts;
   u32 p = 0;
+  // (the tail page and a new page are always HBM pages: only a page found
+  // below the tail selects the tier, so the fast steps' common stores never do)
+  Ent* base = P.pool;
+  u32 first = 0;
   if (cr.tail && pn == cr.tail_pn) {
     p = cr.tail;
   } else if (!cr.tail || pn > cr.tail_pn) {
@@ -181,6 +213,10 @@ RBE_HD bool cold_put(const PL& P, const PA& C, ColdRef& cr, u64 idx, const Ent& 
     cr.tail_pn = pn;
   } else {
     p = cold_find(P, cr, pn);
+    if (p && pool_is_host(P, p)) {
+      base = P.sctl->hpool;
+      first = P.sctl->hpool_first;
+    }
     if (!p) {  // below the tail and missing: a page inserted in order
       p = pool_alloc(P, C, par);
       if (!p) return false;
@@ -197,8 +233,9 @@ RBE_HD bool cold_put(const PL& P, const PA& C, ColdRef& cr, u64 idx, const Ent& 
       else cr.head = p;
     }
   }
-  *pool_ent(P, p, (u32)(idx % kPageEnts)) = e;
-  RBE_AUDIT(AS_COLD_ENT, pool_ent(P, p, (u32)(idx % kPageEnts)), sizeof(Ent));
+  Ent* at = &base[(u64)(p - first) * kPageEnts + (u32)(idx % kPageEnts)];
+  *at = e;
+  RBE_AUDIT(AS_COLD_ENT, at, sizeof(Ent));
   return true;
 }
 // Releases every page whose entries all lie at or below `upto` (LogDB.Compact
@@ -216,6 +253,119 @@ RBE_HD void cold_release(const PL& P, ColdRef& cr, u64 upto, u32 par) {
       cr.tail = 0;
       cr.tail_pn = 0;
     }
+  }
+}
+
+// ---------------------------------------------------------------- host tier
+// Demotion (cfg.host_pool_bytes).  After a round's kernels, while more than
+// half the HBM pool is in use, every replica's committed pages below its
+// chain's tail move to pages of the host tier: the plan (one lane per replica)
+// takes a host page, copies the PoolMeta, relinks the chain and lists the move;
+// the copy (one wave per move) then carries the entries over and gives the HBM
+// page's id to the free-id ring (SpillCtl::fa), which any later round takes from.
+// Nothing is promoted back: a read below the HBM end of a log crosses the
+// host link, a rewrite of an entry there (cold_put below the tail) too, so
+// which pages were chosen never matters for what the engine computes.
+//
+// A host page, or 0 when the tier is full.  Pops and bumps only: the callers
+// (the plan, an import's rebuild) run in kernels that never free a host page.
+template <class PL, class PA>
+RBE_HD u32 host_alloc(const PL& P, const PA& C) {
+  SpillCtl* s = P.sctl;
+  u32* fh = &s->hfree;
+#if defined(__HIP_DEVICE_COMPILE__)
+  u32 h = __hip_atomic_load(fh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  while (h) {
+    const u32 nx = P.pmeta[h].next;
+    const u32 o = atomicCAS(fh, h, nx);
+    if (o == h) break;
+    h = o;
+  }
+  if (!h && __hip_atomic_load(&s->hbump, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <
+                C.host_pages) {
+    // (one atomicAdd; the check keeps the counter within a pass's lanes of host_pages)
+    const u32 b = atomicAdd(&s->hbump, 1u);
+    if (b < C.host_pages) h = s->hpool_first + b;
+  }
+#else
+  u32 h = *fh;
+  if (h) *fh = P.pmeta[h].next;
+  else if (s->hbump < C.host_pages) h = s->hpool_first + s->hbump++;
+#endif
+  if (h) sp_atomic_add_u32(&s->hlive, 1u);
+  return h;
+}
+// The plan for one replica's chain `cr` whose commit index is `commit`, after
+// a round of parity `par`: every HBM page that is not the tail and whose
+// entries all lie at or below `commit` (they never change again) gets a host
+// page and a slot of the move list mv[0, mv_cap) of that parity.  Stops, with
+// the chain whole, when the list or the tier is full; the rest waits for a
+// later pass.  Returns the pages moved.
+template <class PL, class PA>
+RBE_HD u32 cold_demote_plan(const PL& P, const PA& C, ColdRef& cr, u64 commit, u32 par,
+                            ColdMove* mv, u32 mv_cap) {
+  u32 n = 0;
+  for (u32 p = cr.head; p && p != cr.tail;) {
+    const PoolMeta m = P.pmeta[p];
+    if ((m.pn + 1) * kPageEnts - 1 > commit) break;  // (ascending: so are the rest)
+    if (!pool_is_host(P, p)) {
+      // the slot first: a host page taken could not be given back here
+      const u32 slot = sp_atomic_add_u32(&P.sctl->mv_n[par], 1u);
+      if (slot >= mv_cap) break;
+      const u32 h = host_alloc(P, C);
+      ColdMove x;
+      x.src = h ? p : 0u;
+      x.dst = h;
+      mv[slot] = x;  // (a null move when the tier is full)
+      if (!h) break;
+      P.pmeta[h] = m;
+      if (m.prev) P.pmeta[m.prev].next = h;
+      else cr.head = h;
+      P.pmeta[m.next].prev = h;  // (p is not the tail: it has a successor)
+      n++;
+    }
+    p = m.next;
+  }
+  if (n) sp_atomic_add_u64(&P.sctl->demoted, n);
+  return n;
+}
+// the moves of parity `par` to carry out (the counter runs past a full list)
+RBE_HD u32 cold_move_count(const SpillCtl* s, u32 par, u32 mv_cap) {
+  const u32 n = s->mv_n[par];
+  return n < mv_cap ? n : mv_cap;
+}
+// Entry j of move x goes over; cold_demote_done then frees the HBM page
+// (k_cold_demote_copy: a wave per move, a lane per entry, then one lane)
+template <class PL>
+RBE_HD void cold_demote_ent(const PL& P, ColdMove x, u32 j) {
+  const SpillCtl* s = P.sctl;
+  s->hpool[(u64)(x.dst - s->hpool_first) * kPageEnts + j] = P.pool[(u64)x.src * kPageEnts + j];
+}
+template <class PL>
+RBE_HD void cold_demote_done(const PL& P, ColdMove x) {
+  SpillCtl* s = P.sctl;
+  sp_atomic_add_u32(&s->live, ~0u);  // - 1
+  const u32 i = sp_atomic_add_u32(&s->fa_n, 1u);
+  s->fa[(s->fa_base + i) & s->fa_mask] = x.src;
+}
+// Once between two rounds, before the copy appends (one thread; nothing else
+// allocates or frees): the ring entries the bump counter handed out leave the
+// ring's front and the counter goes back to the end of the pool, so it never
+// nears its wrap and the lanes that found the ring empty are forgotten.
+// fa_n never exceeds the free HBM pages, so the ring cannot lap.
+RBE_HD void pool_fa_settle(SpillCtl* s, u32 pool_pages) {
+  if (s->bump <= pool_pages) return;
+  u32 k = s->bump - pool_pages;
+  if (k > s->fa_n) k = s->fa_n;
+  s->fa_base += k;
+  s->fa_n -= k;
+  s->bump = pool_pages;
+}
+// once per pass, after the plan: a pass that moved a page counts
+RBE_HD void cold_demote_account(SpillCtl* s) {
+  if (s->demoted != s->demoted_seen) {
+    s->demoted_seen = s->demoted;
+    s->passes++;
   }
 }
 
@@ -462,7 +612,7 @@ RBE_HD ReadReq* rq_ext_at(const Planes& P, const RqExt& x, u32 i) {
     p = P.pmeta[p].next;
     pos -= kPageEnts;
   }
-  return (ReadReq*)pool_ent(P, p, pos);
+  return (ReadReq*)&P.pool[(u64)p * kPageEnts + pos];  // (queue pages are HBM pages)
 }
 // entry i (< length) of replica r's readIndex queue, wherever it lives
 RBE_HD const ReadReq* rq_entry(const Planes& P, const Params& C, u64 r, const Core& c, u32 i) {

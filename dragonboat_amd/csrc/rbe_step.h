@@ -1604,7 +1604,9 @@ struct Lane {
         P.pmeta[x.tail].next = p;
         x.tail = p;
       }
-      *(ReadReq*)pool_ent(P, x.tail, i % kPageEnts) = P.rq[r * C.rq_cap + rq_wrap((u32)rq_head + i)];
+      // (queue pages are HBM pages: no tier select)
+      *(ReadReq*)&P.pool[(u64)x.tail * kPageEnts + i % kPageEnts] =
+          P.rq[r * C.rq_cap + rq_wrap((u32)rq_head + i)];
       x.n++;
     }
     X().rqd = x;
@@ -1627,7 +1629,7 @@ struct Lane {
       P.pmeta[X().rqd.tail].next = p;
       X().rqd.tail = p;
     }
-    *(ReadReq*)pool_ent(P, X().rqd.tail, pos % kPageEnts) = q;
+    *(ReadReq*)&P.pool[(u64)X().rqd.tail * kPageEnts + pos % kPageEnts] = q;
     X().rqd.n++;
     return true;
   }

@@ -359,20 +359,31 @@ struct Params {
   u64 rl_max;         // config.MaxInMemLogSize (server.NewRateLimiter); 0 = limiter off
   // spill tiers (rbe_spill.h)
   u32 pool_pages;     // pages of the page pool (cold log, readIndex queue beyond rq_cap)
+  u32 host_pages;     // pages of the cold log's host tier (cfg.host_pool_bytes; 0 = no tier);
+                      // (in the padding before spill_units: sizeof(Params) is unchanged)
   u64 spill_units;    // 16-B granules of the round spill heap, per round parity
 };
 
 // Spill tiers (rbe_spill.h).  Page pool: kPageEnts 32-B records a page (log
 // entries of the cold log, or ReadReq of a readIndex queue beyond rq_cap);
 // page 0 is the null page.  PoolMeta links a page into its owner's chain
-// (ascending page numbers), or into a free stack.
+// (ascending page numbers), or into a free stack.  With a host tier
+// (Params::host_pages) page ids [pool_pages, pool_pages + host_pages) name
+// pages of SpillCtl::hpool, host-pinned memory the kernels read in place; their
+// PoolMeta stay in HBM with the others, so a chain walk never leaves the device.
 static constexpr u32 kPageEnts = 64;
 struct alignas(16) PoolMeta {
   u64 pn;         // cold log: the page's entries are [pn * kPageEnts, + kPageEnts)
   u32 prev, next;
 };
 // A replica's cold log: the entries evicted from its term / payload ring, in
-// pages head .. tail (ascending pn); 0 = none
+// pages head .. tail (ascending pn); 0 = none.  Invariant (host tier): `tail`
+// is always an HBM page.  cold_put's tail and new-page stores and cold_put_ol
+// index the HBM pool with it unchecked, so whatever changes a chain's tail
+// must keep it: demotion skips the tail, an import rebuilds the tail in HBM,
+// and a chain loses its tail only by becoming empty (cold_release).
+// tests/test_cold_tier.py::test_model_random_operations checks it after
+// every operation.
 struct alignas(16) ColdRef {
   u32 head, tail;
   u64 tail_pn;
@@ -384,11 +395,41 @@ struct alignas(256) SpillCtl {
   u32 live;          // pages in use
   u32 pad0[61];
   u32 free_head[2];  // free page stacks: a round of parity p frees into [p], takes from [p ^ 1]
-  u32 pad1[62];
+  // the host tier (rbe_spill.h, demotion): its free stack (pushed by the round
+  // kernels, popped only by the demotion plan and an import's rebuild), the
+  // next host page never handed out (an offset from hpool_first), its
+  // pages in use, and the moves planned after a round, by round parity
+  u32 hfree, hbump, hlive;
+  u32 mv_n[2];
+  u32 pad_h;
+  // The tier's constants, set once by rbe_create (all zero: no tier), kept
+  // here and not in Planes / SpillRef so that neither the kernels' arguments
+  // nor the out-of-line tier calls grow with the tier off; only the rare paths
+  // (a read or rewrite below a tail, an exhausted bump counter, a free) load
+  // them.  No atomic of a round kernel lands on this line.
+  Ent* hpool;        // [hpool_pages * kPageEnts] host-pinned, device-mapped
+  u32* fa;           // [fa_mask + 1] ring of the HBM page ids demotion freed (pool_alloc)
+  u32 hpool_first;   // = pool_pages: page id p >= hpool_first is host page p - hpool_first
+  u32 hpool_pages;
+  u32 fa_mask;       // ring size - 1 (a power of two >= pool_pages)
+  // ring entries [fa_base, fa_base + fa_n) (mod the size) are free pages: the
+  // copy kernel appends at fa_n, an exhausted bump counter runs on into them
+  // (pool_alloc), and pool_fa_settle takes what was handed out off the front
+  u32 fa_base, fa_n;
+  u32 pad1[47];
   u64 used[2];       // round spill heap granules handed out, by round parity
   u64 pad2[30];
   u64 peak[2];       // the largest `used` a round reached (diagnostics, rbe_spill_stats)
-  u64 pad3[30];
+  // rbe_cold_tier_stats: pages demoted so far, that count at the last pass
+  // that moved a page, and such passes
+  u64 demoted, demoted_seen, passes;
+  u64 pad3[27];
+};
+static_assert(sizeof(SpillCtl) == 1024, "SpillCtl: four 256-B lines");
+// one planned demotion: the entries of HBM page src go to host page dst
+// (0, 0: a claimed slot the plan could not fill)
+struct ColdMove {
+  u32 src, dst;
 };
 
 // The rate limiter of one replica (internal/server/rate.go:33-137, raft.go:204)

@@ -14,7 +14,7 @@ import numpy as np
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libdragonboat_amd.so")
-RBE_ABI_VERSION = 9
+RBE_ABI_VERSION = 10
 
 COUNTER_NAMES = ["steps", "committed", "msg_in", "msg_out", "ent_in", "ent_out",
                  "reads_confirmed", "proposals", "reads", "quiesced_ticks", "active_ticks",
@@ -49,7 +49,7 @@ class RbeConfig(C.Structure):
                 ("rep_compact", C.c_uint32), ("n_voters", C.c_uint32),
                 ("max_inmem_log_size", C.c_uint64), ("observer_slots", C.c_uint32),
                 ("witness_slots", C.c_uint32), ("pool_bytes", C.c_uint64),
-                ("spill_bytes", C.c_uint64)]
+                ("spill_bytes", C.c_uint64), ("host_pool_bytes", C.c_uint64)]
 
 
 class RbeReplicaView(C.Structure):
@@ -216,7 +216,7 @@ EXPORTS = ["rbe_create", "rbe_destroy", "rbe_abi_version", "rbe_abi_sizes", "rbe
            "rbe_round", "rbe_run_timed", "rbe_prepare_run", "rbe_push_proposals", "rbe_push_read_index",
            "rbe_get_updates", "rbe_get_messages", "rbe_get_ready_to_reads", "rbe_get_entries",
            "rbe_get_views", "rbe_get_counters", "rbe_reset_counters", "rbe_fault_summary",
-           "rbe_spill_stats",
+           "rbe_spill_stats", "rbe_cold_tier_stats",
            "rbe_footprint", "rbe_profile_rounds", "rbe_get_kernel_counters", "rbe_kernel_name",
            "rbe_xchg_record_bytes", "rbe_xchg_pack", "rbe_xchg_unpack", "rbe_get_outbox",
            "rbe_push_messages", "rbe_snapshot_bytes", "rbe_export_bytes", "rbe_export_groups", "rbe_import_groups",
@@ -315,6 +315,7 @@ def load_library(path: Optional[str] = None):
         "rbe_reset_counters": (i32, [vp]),
         "rbe_fault_summary": (i32, [vp, P(u64), P(u32)]),
         "rbe_spill_stats": (i32, [vp, P(u64)]),
+        "rbe_cold_tier_stats": (i32, [vp, P(u64)]),
         "rbe_footprint": (i32, [P(RbeConfig), P(u64)]),
         "rbe_profile_rounds": (i32, [vp, u32, P(C.c_float)]),
         "rbe_get_kernel_counters": (i32, [vp, C.c_int32, P(u64)]),
@@ -365,7 +366,8 @@ def make_config(n_groups: int, n_replicas: int = 3, device: int = 0, election_rt
                 ext_commit: bool = False, membership: bool = False, cc_period: int = 0,
                 cc_mod: int = 1, rep_compact: bool = False,
                 max_inmem_log_size: int = 0, n_voters: int = 0, observer_slots: int = 0,
-                witness_slots: int = 0, pool_bytes: int = 0, spill_bytes: int = 0) -> RbeConfig:
+                witness_slots: int = 0, pool_bytes: int = 0, spill_bytes: int = 0,
+                host_pool_bytes: int = 0) -> RbeConfig:
     return RbeConfig(abi_version=RBE_ABI_VERSION, device=device, n_groups=n_groups,
                      n_replicas=n_replicas, election_rtt=election_rtt,
                      heartbeat_rtt=heartbeat_rtt, check_quorum=int(check_quorum),
@@ -384,7 +386,7 @@ def make_config(n_groups: int, n_replicas: int = 3, device: int = 0, election_rt
                      rep_compact=int(rep_compact), max_inmem_log_size=max_inmem_log_size,
                      n_voters=n_voters, observer_slots=observer_slots,
                      witness_slots=witness_slots, pool_bytes=pool_bytes,
-                     spill_bytes=spill_bytes)
+                     spill_bytes=spill_bytes, host_pool_bytes=host_pool_bytes)
 
 
 class InputError(EngineError):
@@ -1073,6 +1075,14 @@ class Engine(NodeInputs):
         _check(self.lib.rbe_spill_stats(self.h, out), "rbe_spill_stats")
         return dict(pool_pages_used=out[0], pool_pages=out[1], spill_peak_bytes=out[2],
                     spill_bytes=out[3], oom=out[4])
+
+    def cold_tier_stats(self) -> Dict[str, int]:
+        """The cold log's host tier (cfg.host_pool_bytes; rbe_cold_tier_stats):
+        host pages in use / total, pages demoted so far, demotion passes that
+        moved a page.  spill_stats()['pool_pages_used'] counts HBM pages alone."""
+        out = (C.c_uint64 * 4)()
+        _check(self.lib.rbe_cold_tier_stats(self.h, out), "rbe_cold_tier_stats")
+        return dict(host_pages_used=out[0], host_pages=out[1], demoted=out[2], passes=out[3])
 
     def fault_summary(self):
         n = C.c_uint64()

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define RBE_ABI_VERSION 9
+#define RBE_ABI_VERSION 10
 
 /* error codes */
 #define RBE_OK 0
@@ -197,15 +197,25 @@ typedef struct rbe_config {
    * each replica's cold log (its entries below the in-memory ring: the ILogDB
    * read path, logentry.go:144-161, 186-246; every entry above the LogDB
    * marker is kept, as dragonboat's LogDB does) and readIndex queues longer
-   * than rq_cap; 0 = the larger of 8 KiB per replica (at least 64 MiB) and an
-   * eighth of the device's free HBM at rbe_create, at most 32 GiB (rbe_footprint
-   * counts the per-replica part).  spill_bytes: the round spill heap per round
+   * than rq_cap; 0 = 8 KiB per replica, at least 64 MiB and at most 32 GiB
+   * (what rbe_footprint counts), which rbe_create raises to an eighth of the
+   * device's free HBM, at most 32 GiB, when that is more.  spill_bytes: the round spill heap per round
    * parity (message lists past maxm, a message's entries past ecap — a catch-up
    * Replicate sized by MaxEntrySize, raft.go:709-740 — ReadyToReads past
    * rtr_cap, dropped ReadIndexes past dri_cap); 0 = 128 B per replica, at least
    * 16 MiB, at most 4 GiB (times rep_world: each rank allocates in its own share). */
   uint64_t pool_bytes;
   uint64_t spill_bytes;
+  /* Since ABI 10.  A second tier of cold log pages in host-pinned,
+   * device-mapped memory (the reference's LogDB is bounded by disk, not by
+   * memory); 0 = none, and nothing the engine does changes.  With it, after
+   * each round in which more than half the page pool is in use, the committed
+   * pages below the tail of every replica's cold log move there, and the
+   * kernels read (and, rarely, rewrite) them in place over the host link: the
+   * page pool becomes a cache of the recent end of each log.  Nothing moves
+   * back.  Not with rep_world > 1.  RBE_FAULT_NOMEM remains when both tiers
+   * are full (rbe_cold_tier_stats). */
+  uint64_t host_pool_bytes;
 } rbe_config;
 
 /* Snapshot of one replica (tests, debugging, rbe_get_views). */
@@ -766,6 +776,11 @@ int rbe_fault_summary(rbe_engine* e, uint64_t* n_faulty, uint32_t* fault_or);
  * out[4] exhaustion flags (bit 0 the pool, bits 1-2 the heap of parity 0 / 1;
  * sticky, the replicas concerned carry RBE_FAULT_NOMEM). */
 int rbe_spill_stats(rbe_engine* e, uint64_t* out /* 5 */);
+/* The cold log's host tier (cfg.host_pool_bytes), after every round queued:
+ * out[0] host pages in use, out[1] host pages, out[2] pages demoted so far,
+ * out[3] demotion passes that moved at least one page.  All zero without a
+ * tier.  rbe_spill_stats' out[0] counts the page pool's (HBM) pages alone. */
+int rbe_cold_tier_stats(rbe_engine* e, uint64_t* out /* 4 */);
 
 /* Replica-per-GPU mode (cfg.rep_world > 1).  The engine steps
  * only its own replicas; between rounds the host moves the messages of the
