@@ -230,6 +230,10 @@ static int launch_scan(hipStream_t st, const u32* bsum, u32 nb, u64* pre) {
   if (nt > 1) hipLaunchKernelGGL(k_scan_add<Q>, dim3(nt), dim3(kScanThreads), 0, st, nb, pre);
   return hipGetLastError() == hipSuccess ? RBE_OK : RBE_E_HIP;
 }
+// ---- batched entries (rbe_collect_entries / rbe_collect_entry_ranges); the
+// kernels use block_excl_scan and launch_scan above
+#include "rbe_collect_kernels.h"
+
 __global__ __launch_bounds__(kBlock) void k_out_write(Planes P, Params C, u64 first, u64 count,
                                                       u32 round, const u64* pre, u64* moff,
                                                       rbe_message* om, u64* roff,
@@ -808,6 +812,23 @@ struct rbe_engine {
   u64 cs_dev_bytes = 0;
   u8* cs_host = nullptr;
   u64 cs_host_bytes = 0;
+  // rbe_collect_entries / rbe_collect_entry_ranges (ce_collect): device scratch
+  // sized by the ranges (s1) and by the entries (s2), the device lists (meta:
+  // replicas, offsets, records; cmd: the Cmd bytes), and one pinned host copy
+  // per source: EntriesToSave, CommittedEntries, host-named ranges
+  u8* ce_s1 = nullptr;
+  u64 ce_s1_bytes = 0;
+  u8* ce_s2 = nullptr;
+  u64 ce_s2_bytes = 0;
+  u8* ce_meta = nullptr;
+  u64 ce_meta_bytes = 0;
+  u8* ce_cmd = nullptr;
+  u64 ce_cmd_bytes = 0;
+  u8* ce_host[3] = {nullptr, nullptr, nullptr};
+  u64 ce_host_bytes[3] = {0, 0, 0};
+  // whether k_ce_entries stages a block's records in LDS (RBE_COLLECT_STAGE=0:
+  // every lane stores its own)
+  bool ce_stage = true;
   // rbe_collect_step_begin / _end: mapped host memory the write kernel fills
   // directly (header | replicas | updates | offsets | messages | ReadyToReads),
   // its capacities, the pending call and its completion event
@@ -1313,6 +1334,12 @@ int rbe_destroy(rbe_engine* e) {
   for (int i = 0; i < 2; i++)
     if (e->csa_buf[i]) HIP_IGNORE(hipHostFree(e->csa_buf[i]));
   if (e->csa_ev) HIP_IGNORE(hipEventDestroy(e->csa_ev));
+  if (e->ce_s1) HIP_IGNORE(hipFree(e->ce_s1));
+  if (e->ce_s2) HIP_IGNORE(hipFree(e->ce_s2));
+  if (e->ce_meta) HIP_IGNORE(hipFree(e->ce_meta));
+  if (e->ce_cmd) HIP_IGNORE(hipFree(e->ce_cmd));
+  for (int i = 0; i < 3; i++)
+    if (e->ce_host[i]) HIP_IGNORE(hipHostFree(e->ce_host[i]));
   if (e->wire_dev) HIP_IGNORE(hipFree(e->wire_dev));
   if (e->wire_meta) HIP_IGNORE(hipFree(e->wire_meta));
   if (e->wire_rec) HIP_IGNORE(hipFree(e->wire_rec));
@@ -1490,6 +1517,7 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
   }
   HIP_IGNORE(hipMemsetAsync(e->d_clk, 0, 2 * sizeof(u32), e->stream));
   if (const char* wb = getenv("RBE_WIRE_BIG")) e->wire_big = strtoull(wb, nullptr, 10);
+  if (const char* cs = getenv("RBE_COLLECT_STAGE")) e->ce_stage = cs[0] != '0';
   if (const char* fg = getenv("RBE_FAST_GRID")) g_fast_grid = (unsigned)strtoul(fg, nullptr, 10);
   const char* mode = getenv("RBE_MODE");
   // default: k_triage → k_fast_both → k_full_list; RBE_MODE=split runs the two
@@ -3009,6 +3037,179 @@ int rbe_get_entry_cmds(rbe_engine* e, uint64_t replica, uint64_t lo, uint64_t hi
   }
   HIP_OK(hipStreamSynchronize(e->stream));
   return RBE_OK;
+}
+
+// rbe_collect_entries / rbe_collect_entry_ranges: the ranges of `s` (with
+// h_rep / h_lo / h_hi the host's triples of the ranges form), their entries
+// and, with `cmds`, the Cmd bytes, into the pinned buffer of source `slot`.
+// Whatever the ranges hold, a call is at most 12 kernel launches and a memset,
+// 10 copies (3 up for the ranges form, the totals, the Cmd total, the lists,
+// the Cmd bytes, the error word with each of the 3 waits) and 3 stream
+// synchronisations; when heap records are still staged for the next step, two
+// more copies at most and one more wait bring them to the device first.
+static int ce_collect(rbe_engine* e, CeSrc s, const u64* h_rep, const u64* h_lo, const u64* h_hi,
+                      bool cmds, u32 slot, rbe_entry_list* out) {
+  HIP_OK(hipSetDevice(e->device));
+  auto al = [](u64 x) { return (x + 255) & ~255ull; };
+  const u64 count = s.count;
+  const u32 nb = grid_for(count);
+  // scratch 1: error word | block sums (pairs) | block prefixes (+ totals) | triples
+  const u64 o_bs = 256, o_pre = o_bs + al(2ull * nb * sizeof(u32));
+  const u64 o_tri = o_pre + al(scan_words(2, nb) * sizeof(u64)), tri = al(count * sizeof(u64));
+  int rc = grow(&e->ce_s1, &e->ce_s1_bytes, o_tri + (h_rep ? 3 * tri : 0), false);
+  if (rc) return rc;
+  u32* err = (u32*)e->ce_s1;
+  u32* bsum = (u32*)(e->ce_s1 + o_bs);
+  u64* pre = (u64*)(e->ce_s1 + o_pre);
+  HIP_OK(hipMemsetAsync(err, 0, sizeof(u32), e->stream));
+  // Heap records still staged for the next step (an rbe_launch's, whose
+  // entries k_relaunch has already put into the logs; proposals not yet
+  // stepped) go to the device heap now, at the positions the next flush writes
+  // them to again: the push that staged them checked that they lap no live
+  // record (HostHeap::room), and the kernels judge every record by the host's
+  // head, as read_heap does.  The wait keeps the stage's memory from changing
+  // under the copy.
+  if (HostHeap& hp = e->hin.heap; hp.cap && hp.flushed < hp.head) {
+    for (u64 p = hp.flushed; p < hp.head;) {
+      const u64 at = p % hp.cap, len = std::min(hp.head - p, hp.cap - at);
+      HIP_OK(hipMemcpyAsync(e->heap + at, hp.stage.data() + (p - hp.flushed), len,
+                            hipMemcpyHostToDevice, e->stream));
+      p += len;
+    }
+    HIP_OK(hipStreamSynchronize(e->stream));
+  }
+  if (h_rep) {
+    u64* d = (u64*)(e->ce_s1 + o_tri);
+    HIP_OK(hipMemcpyAsync(d, h_rep, count * sizeof(u64), hipMemcpyHostToDevice, e->stream));
+    HIP_OK(hipMemcpyAsync(d + tri / 8, h_lo, count * sizeof(u64), hipMemcpyHostToDevice, e->stream));
+    HIP_OK(hipMemcpyAsync(d + 2 * (tri / 8), h_hi, count * sizeof(u64), hipMemcpyHostToDevice,
+                          e->stream));
+    s.rep = d;
+    s.lo = d + tri / 8;
+    s.hi = d + 2 * (tri / 8);
+  }
+  hipLaunchKernelGGL(k_ce_count, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C, s, bsum, err);
+  if ((rc = launch_scan<2>(e->stream, bsum, nb, pre))) return rc;
+  u64 tot[2];
+  u32 herr = 0;
+  HIP_OK(hipMemcpyAsync(tot, pre + 2ull * nb, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  if (herr) return collect_rc(herr);
+  const u64 n = tot[0], ne = tot[1];
+  const u32 nb2 = ne ? grid_for(ne) : 1u;
+  // the lists, laid out on the device as in the host copy: replicas | entry
+  // offsets | records (room for whole blocks of them) | Cmd offsets
+  const u64 m_eoff = al(n * sizeof(u64)), m_ent = m_eoff + al((n + 1) * sizeof(u64));
+  const u64 m_coff = m_ent + al((u64)nb2 * kBlock * sizeof(rbe_entry));
+  const u64 m_end = m_coff + (cmds ? al((ne + 1) * sizeof(u64)) : 0);
+  if ((rc = grow(&e->ce_meta, &e->ce_meta_bytes, m_end, false))) return rc;
+  // scratch 2: each range's first index | padded Cmd lengths | Cmd sources |
+  // block sums | block prefixes (+ the Cmd total)
+  const u64 o_len = al(n * sizeof(u64)), o_src = o_len + al(ne * sizeof(u32));
+  const u64 o_bs2 = o_src + al(ne * sizeof(u64)), o_pre2 = o_bs2 + al(2ull * nb2 * sizeof(u32));
+  if ((rc = grow(&e->ce_s2, &e->ce_s2_bytes, o_pre2 + al(scan_words(2, nb2) * sizeof(u64)), false)))
+    return rc;
+  u8* m = e->ce_meta;
+  u64* lo_at = (u64*)e->ce_s2;
+  u32* plen = (u32*)(e->ce_s2 + o_len);
+  u64* src = (u64*)(e->ce_s2 + o_src);
+  u32* bsum2 = (u32*)(e->ce_s2 + o_bs2);
+  u64* pre2 = (u64*)(e->ce_s2 + o_pre2);
+  CeCaps caps{n, ne, 0};
+  hipLaunchKernelGGL(k_ce_ranges, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C, s,
+                     (const u64*)pre, (u64*)m, (u64*)(m + m_eoff), lo_at, caps, err);
+  if (ne) {
+    const unsigned g = std::min(nb2, kCeGrid);
+    auto k = e->ce_stage ? k_ce_entries<true> : k_ce_entries<false>;
+    hipLaunchKernelGGL(k, dim3(g), dim3(kBlock), 0, e->stream, e->P, e->C, (const u8*)e->heap,
+                       (u64)e->hin.heap.head, (const u64*)(pre + 2ull * nb), (const u64*)m, (const u64*)(m + m_eoff),
+                       (const u64*)lo_at, (rbe_entry*)(m + m_ent), plen, src, caps, err);
+  }
+  u64 cmd_bytes = 0;
+  if (cmds) {
+    hipLaunchKernelGGL(k_ce_cmd_sum, dim3(nb2), dim3(kBlock), 0, e->stream, (const u32*)plen, ne,
+                       bsum2);
+    if ((rc = launch_scan<2>(e->stream, bsum2, nb2, pre2))) return rc;
+    hipLaunchKernelGGL(k_ce_cmd_off, dim3(nb2), dim3(kBlock), 0, e->stream, (const u32*)plen, ne,
+                       (const u64*)pre2, (u64*)(m + m_coff));
+    u64 units = 0;
+    HIP_OK(hipMemcpyAsync(&units, pre2 + 2ull * nb2, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    if (herr) return collect_rc(herr);
+    cmd_bytes = units * 16;
+    if ((rc = grow(&e->ce_cmd, &e->ce_cmd_bytes, cmd_bytes, false))) return rc;
+    caps.cmd = cmd_bytes;
+    if (cmd_bytes)
+      hipLaunchKernelGGL(k_ce_cmds, dim3(std::min(nb2, kCeCmdGrid)),  // (4 waves a block)
+                         dim3(kBlock), 0, e->stream, (const u8*)e->heap, ne,
+                         (const rbe_entry*)(m + m_ent), (const u64*)src,
+                         (const u64*)(m + m_coff), e->ce_cmd, caps);
+  }
+  HIP_OK(hipGetLastError());
+  if ((rc = grow(&e->ce_host[slot], &e->ce_host_bytes[slot], m_end + al(cmd_bytes), true)))
+    return rc;
+  u8* h = e->ce_host[slot];
+  HIP_OK(hipMemcpyAsync(h, m, m_end, hipMemcpyDeviceToHost, e->stream));
+  if (cmd_bytes)
+    HIP_OK(hipMemcpyAsync(h + m_end, e->ce_cmd, cmd_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  if (herr) return collect_rc(herr);
+  out->n = n;
+  out->n_entries = ne;
+  out->cmd_bytes = cmd_bytes;
+  out->replica = (const uint64_t*)h;
+  out->ent_off = (const uint64_t*)(h + m_eoff);
+  out->entries = (const rbe_entry*)(h + m_ent);
+  if (cmds) {
+    out->cmd_off = (const uint64_t*)(h + m_coff);
+    out->cmds = (const uint8_t*)(h + m_end);
+  }
+  return RBE_OK;
+}
+
+int rbe_collect_entries(rbe_engine* e, uint64_t first, uint64_t count, uint32_t flags,
+                        rbe_entry_list* out) {
+  const uint32_t which = flags & (RBE_ENTRIES_TO_SAVE | RBE_ENTRIES_COMMITTED);
+  if (!e || !out || count == 0 || first >= e->C.n_rep || count > e->C.n_rep - first ||
+      (flags & ~(RBE_ENTRIES_TO_SAVE | RBE_ENTRIES_COMMITTED | RBE_ENTRIES_NO_CMDS)) ||
+      (which != RBE_ENTRIES_TO_SAVE && which != RBE_ENTRIES_COMMITTED))
+    return RBE_E_INVALID;
+  memset(out, 0, sizeof(*out));
+  out->first = first;
+  out->count = count;
+  static const uint64_t zero = 0;
+  if (e->round == 0) {  // no round has run: no Update, empty lists
+    out->ent_off = &zero;
+    if (!(flags & RBE_ENTRIES_NO_CMDS)) out->cmd_off = &zero;
+    return RBE_OK;
+  }
+  CeSrc s{first, count, e->round, which, nullptr, nullptr, nullptr};
+  const int rc = ce_collect(e, s, nullptr, nullptr, nullptr, !(flags & RBE_ENTRIES_NO_CMDS),
+                            which == RBE_ENTRIES_TO_SAVE ? 0u : 1u, out);
+  if (rc) memset(out, 0, sizeof(*out));
+  return rc;
+}
+
+int rbe_collect_entry_ranges(rbe_engine* e, uint64_t n, const uint64_t* replica,
+                             const uint64_t* lo, const uint64_t* hi, uint32_t flags,
+                             rbe_entry_list* out) {
+  if (!e || !out || (flags & ~RBE_ENTRIES_NO_CMDS) || (n && (!replica || !lo || !hi)))
+    return RBE_E_INVALID;
+  memset(out, 0, sizeof(*out));
+  out->count = n;
+  static const uint64_t zero = 0;
+  if (n == 0) {
+    out->ent_off = &zero;
+    if (!(flags & RBE_ENTRIES_NO_CMDS)) out->cmd_off = &zero;
+    return RBE_OK;
+  }
+  CeSrc s{0, n, e->round, 0, nullptr, nullptr, nullptr};
+  const int rc = ce_collect(e, s, replica, lo, hi, !(flags & RBE_ENTRIES_NO_CMDS), 2u, out);
+  if (rc) memset(out, 0, sizeof(*out));
+  return rc;
 }
 
 int rbe_spill_stats(rbe_engine* e, uint64_t* out) {

@@ -204,6 +204,17 @@ class RbeUpdateList(C.Structure):
                 ("replica", C.POINTER(C.c_uint64)), ("updates", C.POINTER(RbeUpdate))]
 
 
+class RbeEntryList(C.Structure):
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("n", C.c_uint64),
+                ("n_entries", C.c_uint64), ("cmd_bytes", C.c_uint64),
+                ("replica", C.POINTER(C.c_uint64)), ("ent_off", C.POINTER(C.c_uint64)),
+                ("entries", C.POINTER(RbeEntry)), ("cmd_off", C.POINTER(C.c_uint64)),
+                ("cmds", C.POINTER(C.c_uint8))]
+
+
+RBE_ENTRIES_TO_SAVE, RBE_ENTRIES_COMMITTED, RBE_ENTRIES_NO_CMDS = 1, 2, 0x100
+
+ENTRY_DTYPE = _np_dtype(RbeEntry)
 MESSAGE_DTYPE = _np_dtype(RbeMessage)
 UPDATE_DTYPE = _np_dtype(RbeUpdate)
 RTR_DTYPE = _np_dtype(RbeReadyToRead)
@@ -227,7 +238,8 @@ EXPORTS = ["rbe_create", "rbe_destroy", "rbe_abi_version", "rbe_abi_sizes", "rbe
            "rbe_get_update_commits", "rbe_get_update_snapshots", "rbe_replace_node", "rbe_propose_config_change", "rbe_apply_config_change",
            "rbe_reject_config_change", "rbe_rate_limited", "rbe_restore_remotes",
            "rbe_snapshot_saved", "rbe_compact", "rbe_set_node_ids", "rbe_collect_step",
-           "rbe_collect_step_begin", "rbe_collect_step_end"]
+           "rbe_collect_step_begin", "rbe_collect_step_end", "rbe_collect_entries",
+           "rbe_collect_entry_ranges"]
 KERNEL_SLOTS = 4
 
 _lib = None
@@ -291,6 +303,9 @@ def load_library(path: Optional[str] = None):
         "rbe_collect_step": (i32, [vp, u64, u64, u32, P(RbeStepOutputs)]),
         "rbe_collect_step_begin": (i32, [vp, u64, u64, u32]),
         "rbe_collect_step_end": (i32, [vp, P(RbeStepOutputs)]),
+        "rbe_collect_entries": (i32, [vp, u64, u64, u32, P(RbeEntryList)]),
+        "rbe_collect_entry_ranges": (i32, [vp, u64, P(u64), P(u64), P(u64), u32,
+                                           P(RbeEntryList)]),
         "rbe_get_messages": (i32, [vp, u64, P(RbeMessage), u32, P(u32)]),
         "rbe_get_outbox": (i32, [vp, u64, P(RbeMessage), u32, P(u32), P(RbeEntry), u32, P(u32),
                                  vp, u64, P(u64)]),
@@ -466,6 +481,41 @@ def entry_cmds(fn, h, replica: int, lo: int, hi: int) -> List[bytes]:
     _check(fn(h, replica, lo, hi, buf, total, offs), "rbe_get_entry_cmds")
     raw = buf.raw
     return [raw[offs[i]:offs[i + 1]] for i in range(hi - lo + 1)]
+
+
+def entry_list_call(fn, what, *args):
+    """rbe_collect_entries / rbe_collect_entry_ranges (or the host build's):
+    (replica, ent_off, entries as ENTRY_DTYPE, cmd_off, cmds as uint8), numpy
+    copies of the engine's buffers; cmd_off and cmds are None when the call
+    returned none (RBE_ENTRIES_NO_CMDS)."""
+    o = RbeEntryList()
+    rc = fn(*args, C.byref(o))
+    if rc != 0:
+        e = EngineError(f"{what} failed with rc={rc}")
+        e.rc = rc
+        raise e
+
+    def arr(ptr, n, dtype):
+        if n == 0 or not ptr:
+            return np.zeros(0, dtype=dtype)
+        raw = C.string_at(C.cast(ptr, C.c_void_p), n * np.dtype(dtype).itemsize)
+        return np.frombuffer(raw, dtype=dtype).copy()
+
+    rep = arr(o.replica, o.n, np.uint64)
+    eoff = arr(o.ent_off, o.n + 1, np.uint64)
+    ents = arr(o.entries, o.n_entries, ENTRY_DTYPE)
+    if not o.cmd_off:
+        return rep, eoff, ents, None, None
+    return rep, eoff, ents, arr(o.cmd_off, o.n_entries + 1, np.uint64), arr(o.cmds, o.cmd_bytes,
+                                                                          np.uint8)
+
+
+def entry_ranges_args(replicas, los, his):
+    r, a, b = (np.ascontiguousarray(x, np.uint64) for x in (replicas, los, his))
+    if not (len(r) == len(a) == len(b)):
+        raise ValueError("replicas, los and his differ in length")
+    p = C.POINTER(C.c_uint64)
+    return (len(r), r.ctypes.data_as(p), a.ctypes.data_as(p), b.ctypes.data_as(p)), (r, a, b)
 
 
 def outbox_call(fn, h, replica, cap, ent_cap, cmd_cap):
@@ -1066,6 +1116,24 @@ class Engine(NodeInputs):
 
     def entry_cmds(self, replica: int, lo: int, hi: int) -> List[bytes]:
         return entry_cmds(self.lib.rbe_get_entry_cmds, self.h, replica, lo, hi)
+
+    def collect_entries(self, first: int = 0, count: Optional[int] = None,
+                        which: int = RBE_ENTRIES_TO_SAVE, cmds: bool = True):
+        """rbe_collect_entries: the EntriesToSave (RBE_ENTRIES_TO_SAVE) or
+        CommittedEntries (RBE_ENTRIES_COMMITTED) of the last round's Updates of
+        replicas [first, first + count), gathered on the device in one call:
+        (replica, ent_off, entries, cmd_off, cmds) as entry_list_call returns."""
+        count = self.n_rep - first if count is None else count
+        return entry_list_call(self.lib.rbe_collect_entries, "rbe_collect_entries", self.h, first,
+                               count, which | (0 if cmds else RBE_ENTRIES_NO_CMDS))
+
+    def collect_entry_ranges(self, replicas, los, his, cmds: bool = True):
+        """rbe_collect_entry_ranges: entries [los[i], his[i]] of replicas[i]
+        for every i in one call (the batched rbe_get_entries +
+        rbe_get_entry_cmds), as collect_entries returns them."""
+        args, keep = entry_ranges_args(replicas, los, his)
+        return entry_list_call(self.lib.rbe_collect_entry_ranges, "rbe_collect_entry_ranges",
+                               self.h, *args, 0 if cmds else RBE_ENTRIES_NO_CMDS)
 
     def spill_stats(self) -> Dict[str, int]:
         """The spill tiers' use (rbe_spill_stats): pool pages in use / total,

@@ -763,6 +763,61 @@ int rbe_collect_step(rbe_engine* e, uint64_t first, uint64_t count, uint32_t fla
  * round) until the one after it, or rbe_destroy. */
 int rbe_collect_step_begin(rbe_engine* e, uint64_t first, uint64_t count, uint32_t flags);
 int rbe_collect_step_end(rbe_engine* e, rbe_step_outputs* out);
+/* The entries the Updates name only as index ranges, and their Cmds, for many
+ * replicas in one call: what the node loop hands to logdb.SaveRaftState in one
+ * batch (execengine.go:523) and to the state machine (node.go:959-977).  The
+ * batched form of rbe_get_entries + rbe_get_entry_cmds: gathered on the device
+ * (a lane per entry, from the ring, the cold log's pages in HBM or in its host
+ * tier, and the payload heap) and copied into engine-owned pinned buffers with
+ * a fixed number of launches, copies and waits, however many replicas and
+ * entries are listed.
+ *   rbe_collect_entries reads the last round's Update of replicas [first,
+ *     first + count) and lists, replicas ascending, those whose
+ *     EntriesToSave (RBE_ENTRIES_TO_SAVE) or CommittedEntries
+ *     (RBE_ENTRIES_COMMITTED) range is not empty, with the entries of that
+ *     range.  Exactly one of the two flags (RBE_E_INVALID otherwise).  A
+ *     replica this engine does not step (rep_world > 1) has no Update and is
+ *     not listed; with rep_compact the indexes are the local ones.  Before the
+ *     first step the lists are empty.
+ *   rbe_collect_entry_ranges lists entries [lo[i], hi[i]] of replica[i], in
+ *     call order (a LogDB-style read: everything a lagging state machine still
+ *     has to apply).  lo == 0, hi < lo, hi above the replica's last index or a
+ *     replica out of range is RBE_E_INVALID for the whole call.
+ * replica[i] owns entries[ent_off[i] .. ent_off[i + 1]), Index ascending,
+ * every field filled as rbe_get_entries fills it; entry j's Cmd is cmds[
+ * cmd_off[j] .. cmd_off[j] + entries[j].cmd_len), each cmd_off a multiple of
+ * 16 and the bytes up to the next one zero.  With RBE_ENTRIES_NO_CMDS cmd_off
+ * and cmds are null and no Cmd byte beyond the records' first 16 is read.  An
+ * entry a replica no longer holds — compacted, below what a launch handed
+ * over, or with a heap record a later lap overwrote — makes the whole call
+ * RBE_E_STATE with *out zeroed, as rbe_get_entries answers (ErrCompacted).
+ * A record still staged for the next step (the entries of an rbe_launch
+ * before the step after it) is served like any other.  A call lists fewer than
+ * 2^32 entries and less than 64 GiB of Cmd bytes.  There
+ * is one set of buffers per source (EntriesToSave, CommittedEntries, ranges),
+ * so a node can hold a round's save list and committed list together; a list
+ * stays valid until the next collection from the same source, the next
+ * rbe_step / rbe_run, or rbe_destroy.  The calls run on the engine's stream
+ * and may come between rbe_collect_step_begin and _end. */
+#define RBE_ENTRIES_TO_SAVE   1u      /* Update.EntriesToSave    [save_lo,  save_hi]  */
+#define RBE_ENTRIES_COMMITTED 2u      /* Update.CommittedEntries [apply_lo, apply_hi] */
+#define RBE_ENTRIES_NO_CMDS   0x100u  /* records only (rbe_entry.cmd keeps the first 16 bytes) */
+typedef struct rbe_entry_list {
+  uint64_t first, count;     /* the replica range asked for (ranges form: 0, n) */
+  uint64_t n;                /* replicas (ranges) listed */
+  uint64_t n_entries, cmd_bytes;
+  const uint64_t* replica;   /* n; ascending (ranges form: call order) */
+  const uint64_t* ent_off;   /* n + 1: replica[i] owns entries[ent_off[i] .. ent_off[i+1]) */
+  const rbe_entry* entries;  /* n_entries, Index ascending within a replica, every field */
+  const uint64_t* cmd_off;   /* n_entries + 1, each a multiple of 16; entry j's Cmd is
+                                cmds[cmd_off[j] .. cmd_off[j] + entries[j].cmd_len) */
+  const uint8_t* cmds;       /* cmd_bytes = cmd_off[n_entries] */
+} rbe_entry_list;
+int rbe_collect_entries(rbe_engine* e, uint64_t first, uint64_t count, uint32_t flags,
+                        rbe_entry_list* out);
+int rbe_collect_entry_ranges(rbe_engine* e, uint64_t n, const uint64_t* replica,
+                             const uint64_t* lo, const uint64_t* hi, uint32_t flags,
+                             rbe_entry_list* out);
 int rbe_get_counters(rbe_engine* e, uint64_t* out /* RBE_CTR_NUM */);
 /* the counters one pipeline kernel (RBE_KERNEL_*) contributed */
 int rbe_get_kernel_counters(rbe_engine* e, int32_t kernel, uint64_t* out /* RBE_CTR_NUM */);
