@@ -233,6 +233,9 @@ static int launch_scan(hipStream_t st, const u32* bsum, u32 nb, u64* pre) {
 // ---- batched entries (rbe_collect_entries / rbe_collect_entry_ranges); the
 // kernels use block_excl_scan and launch_scan above
 #include "rbe_collect_kernels.h"
+// ---- self-contained checkpoints (rbe_export_groups_ex, the heap section of
+// rbe_import_groups); the kernels use block_excl_scan and launch_scan above
+#include "rbe_checkpoint_kernels.h"
 
 __global__ __launch_bounds__(kBlock) void k_out_write(Planes P, Params C, u64 first, u64 count,
                                                       u32 round, const u64* pre, u64* moff,
@@ -829,6 +832,22 @@ struct rbe_engine {
   // whether k_ce_entries stages a block's records in LDS (RBE_COLLECT_STAGE=0:
   // every lane stores its own)
   bool ce_stage = true;
+  // rbe_export_groups_ex and the heap section of rbe_import_groups (ck_export,
+  // ck_import_heap): scratch sized by the replicas (s), the flat page list, the
+  // gathered log section, the reference pairs with their sort and scan scratch,
+  // the heap section, and the pinned host copy of both sections
+  u8* ck_s = nullptr;
+  u64 ck_s_bytes = 0;
+  u8* ck_list = nullptr;
+  u64 ck_list_bytes = 0;
+  u8* ck_log = nullptr;
+  u64 ck_log_bytes = 0;
+  u8* ck_ref = nullptr;
+  u64 ck_ref_bytes = 0;
+  u8* ck_sec = nullptr;
+  u64 ck_sec_bytes = 0;
+  u8* ck_host = nullptr;
+  u64 ck_host_bytes = 0;
   // rbe_collect_step_begin / _end: mapped host memory the write kernel fills
   // directly (header | replicas | updates | offsets | messages | ReadyToReads),
   // its capacities, the pending call and its completion event
@@ -1167,7 +1186,220 @@ static int snap_range_spilled(rbe_engine* e, u64 first, u64 count, bool* out) {
   return RBE_OK;
 }
 
+// Heap records still staged for the next step go to the device heap now, at
+// the positions the next flush writes them to again (ce_collect's upload: the
+// wait keeps the stage's memory from changing under the copy)
+static int heap_upload_staged(rbe_engine* e) {
+  HostHeap& hp = e->hin.heap;
+  if (!hp.cap || hp.flushed >= hp.head) return RBE_OK;
+  for (u64 p = hp.flushed; p < hp.head;) {
+    const u64 at = p % hp.cap, len = std::min(hp.head - p, hp.cap - at);
+    HIP_OK(hipMemcpyAsync(e->heap + at, hp.stage.data() + (p - hp.flushed), len,
+                          hipMemcpyHostToDevice, e->stream));
+    p += len;
+  }
+  HIP_OK(hipStreamSynchronize(e->stream));
+  return RBE_OK;
+}
+
+// rbe_export_groups_ex: the log section gathered on the device and, with
+// `want_heap`, the heap section after it (rbe_checkpoint.h), into engine-owned
+// pinned memory and then into buf; the planes as rbe_export_groups copies them.
+// Whatever the range holds, a call is at most 15 kernel launches and one device
+// radix sort, 2 memsets, 11 small copies down (3 of them the round-spill
+// check's rows) and the two sections', one 2-D copy per plane, and 6 stream
+// synchronisations (8 launches, 1 memset and 4 synchronisations without the
+// heap section); heap records still staged for the next step cost two more
+// copies up and a wait.
+static int ck_export(rbe_engine* e, u64 first, u64 count, bool want_heap, void* buf, u64 cap,
+                     u64* bytes) {
+  auto al = [](u64 x) { return (x + 255) & ~255ull; };
+  const Params& C = e->C;
+  const u64 body = snap_body_bytes(e->P, C, count), r0 = first * C.n, nr = count * C.n;
+  HIP_OK(hipSetDevice(e->device));
+  bool spilled = false;
+  int rc = snap_range_spilled(e, first, count, &spilled);
+  if (rc) return rc;
+  if (spilled) return RBE_E_STATE;
+  const bool heap = want_heap && C.heap_bytes;
+  if (heap && (rc = heap_upload_staged(e))) return rc;
+  const u64 head = e->hin.heap.head;
+  // scratch: error word | reference counter | block sums (pairs) | block prefixes (+ totals)
+  const u32 nb = grid_for(nr);
+  const u64 o_cnt = 256, o_bs = 512, o_pre = o_bs + al(2ull * nb * sizeof(u32));
+  if ((rc = grow(&e->ck_s, &e->ck_s_bytes, o_pre + al(scan_words(2, nb) * sizeof(u64)), false)))
+    return rc;
+  u32* err = (u32*)e->ck_s;
+  unsigned long long* cnt = (unsigned long long*)(e->ck_s + o_cnt);
+  u32* bsum = (u32*)(e->ck_s + o_bs);
+  u64* pre = (u64*)(e->ck_s + o_pre);
+  HIP_OK(hipMemsetAsync(e->ck_s, 0, 512, e->stream));
+  hipLaunchKernelGGL(k_ck_count, dim3(nb), dim3(kBlock), 0, e->stream, e->P, C, r0, nr, bsum);
+  if ((rc = launch_scan<2>(e->stream, bsum, nb, pre))) return rc;
+  u64 tot[2];
+  u32 herr = 0;
+  HIP_OK(hipMemcpyAsync(tot, pre + 2ull * nb, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  const u64 np = tot[0], lb = tot[1] * 16;
+  if ((rc = grow(&e->ck_list, &e->ck_list_bytes, (np + 1) * sizeof(CkPage), false))) return rc;
+  if ((rc = grow(&e->ck_log, &e->ck_log_bytes, lb + 16, false))) return rc;
+  CkPage* list = (CkPage*)e->ck_list;
+  CkCaps caps{np, tot[1], 0};
+  hipLaunchKernelGGL(k_ck_replicas, dim3(nb), dim3(kBlock), 0, e->stream, e->P, C, r0, nr,
+                     (const u64*)pre, e->ck_log, list, caps, err);
+  if (np)
+    hipLaunchKernelGGL(k_ck_pages, dim3(std::min(grid_for(np * 64), kCkPageGrid)), dim3(kBlock), 0,
+                       e->stream, e->P, (const u64*)(pre + 2ull * nb), (const CkPage*)list,
+                       e->ck_log, caps);
+  HIP_OK(hipGetLastError());
+  u64 hb = 0;
+  if (heap) {
+    const u64 n_all = np * kPageEnts + nr * C.ring + nr;
+    const unsigned g = std::min(grid_for(n_all), kCkRefGrid);
+    hipLaunchKernelGGL(k_ck_refs<false>, dim3(g), dim3(kBlock), 0, e->stream, e->P, C, r0, nr,
+                       e->round, head, (const u64*)(pre + 2ull * nb), (const CkPage*)list,
+                       (const u8*)e->ck_log, (u64*)nullptr, (u32*)nullptr, cnt, caps, err);
+    HIP_OK(hipGetLastError());
+    u64 n_ref = 0;
+    HIP_OK(hipMemcpyAsync(&n_ref, cnt, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    if (herr) return RBE_E_STATE;
+    if (n_ref > 0x7FFFFFFFull) return RBE_E_NOMEM;  // (the sort counts in 31 bits)
+    const u32 nb2 = n_ref ? grid_for(n_ref) : 1u;
+    int bits = 1;
+    while (bits < 64 && (head >> bits)) bits++;
+    size_t tb = 0;
+    if (n_ref && dev_sort_pairs(nullptr, &tb, nullptr, nullptr, nullptr, nullptr, n_ref, bits, e->stream))
+      return RBE_E_HIP;
+    // pairs | sorted pairs | record offsets | block sums | block prefixes | sort temporary
+    const u64 o_sk = al(n_ref * 8), o_v = o_sk + al(n_ref * 8), o_sv = o_v + al(n_ref * 4);
+    const u64 o_ro = o_sv + al(n_ref * 4), o_bs2 = o_ro + al((n_ref + 1) * 8);
+    const u64 o_pre2 = o_bs2 + al(2ull * nb2 * sizeof(u32));
+    const u64 o_tmp = o_pre2 + al(scan_words(2, nb2) * sizeof(u64));
+    if ((rc = grow(&e->ck_ref, &e->ck_ref_bytes, o_tmp + al(tb), false))) return rc;
+    u8* b = e->ck_ref;
+    u64 *keys = (u64*)b, *skeys = (u64*)(b + o_sk), *rec_off = (u64*)(b + o_ro);
+    u32 *vals = (u32*)(b + o_v), *svals = (u32*)(b + o_sv), *bsum2 = (u32*)(b + o_bs2);
+    u64* pre2 = (u64*)(b + o_pre2);
+    caps.refs = n_ref;
+    if (n_ref) {
+      HIP_OK(hipMemsetAsync(cnt, 0, sizeof(u64), e->stream));
+      hipLaunchKernelGGL(k_ck_refs<true>, dim3(g), dim3(kBlock), 0, e->stream, e->P, C, r0, nr,
+                         e->round, head, (const u64*)(pre + 2ull * nb), (const CkPage*)list,
+                         (const u8*)e->ck_log, keys, vals, cnt, caps, err);
+      HIP_OK(hipGetLastError());
+      if (dev_sort_pairs(b + o_tmp, &tb, keys, skeys, vals, svals, n_ref, bits, e->stream))
+        return RBE_E_HIP;
+    }
+    hipLaunchKernelGGL(k_ck_heads, dim3(nb2), dim3(kBlock), 0, e->stream, (const u64*)skeys,
+                       (const u32*)svals, n_ref, bsum2, err);
+    if ((rc = launch_scan<2>(e->stream, bsum2, nb2, pre2))) return rc;
+    u64 rt[2];
+    HIP_OK(hipMemcpyAsync(rt, pre2 + 2ull * nb2, sizeof(rt), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    if (herr) return RBE_E_STATE;  // (CK_CONFLICT: two lengths for one record)
+    const u64 n_rec = rt[0], units = rt[1];
+    const u64 o_recs = sizeof(SnapHeapHdr) + n_rec * sizeof(SnapHeapRow);
+    hb = o_recs + units * 16;
+    if ((rc = grow(&e->ck_sec, &e->ck_sec_bytes, hb, false))) return rc;
+    hipLaunchKernelGGL(k_ck_table, dim3(nb2), dim3(kBlock), 0, e->stream, (const u64*)skeys,
+                       (const u32*)svals, n_ref, (const u64*)pre2, head, (u64)C.heap_bytes,
+                       e->ck_sec, rec_off, n_rec, err);
+    if (units)
+      hipLaunchKernelGGL(k_ck_records<CK_GATHER>, dim3(std::min(grid_for(units), kCkRecGrid)),
+                         dim3(kBlock), 0, e->stream, e->heap, (u64)C.heap_bytes,
+                         (const SnapHeapRow*)(e->ck_sec + sizeof(SnapHeapHdr)),
+                         (const u64*)rec_off, n_rec, e->ck_sec + o_recs, units, err);
+    HIP_OK(hipGetLastError());
+  }
+  const u64 total = snap_log_at(body) + lb + hb;
+  *bytes = total;
+  const bool fill = buf && cap >= total;
+  if (fill) {
+    if ((rc = grow(&e->ck_host, &e->ck_host_bytes, lb + hb, true))) return rc;
+    if (lb) HIP_OK(hipMemcpyAsync(e->ck_host, e->ck_log, lb, hipMemcpyDeviceToHost, e->stream));
+    if (hb)
+      HIP_OK(hipMemcpyAsync(e->ck_host + lb, e->ck_sec, hb, hipMemcpyDeviceToHost, e->stream));
+  }
+  HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  if (herr) return RBE_E_STATE;
+  if (!fill) return RBE_E_NOMEM;
+  SnapHeader h;
+  snap_fill_header(C, RBE_ABI_VERSION, e->round, e->tclk, first, count, body, &h);
+  h.log_bytes = lb;
+  memcpy(buf, &h, sizeof(h));
+  memset((u8*)buf + sizeof(h) + body, 0, snap_log_at(body) - sizeof(h) - body);
+  memcpy((u8*)buf + snap_log_at(body), e->ck_host, lb + hb);
+  SnapPlane pl[kSnapPlanes];
+  snap_planes(e->P, C, pl);
+  u8* dst = (u8*)buf + sizeof(SnapHeader);
+  for (int i = 0; i < kSnapPlanes && pl[i].rows; i++) {
+    const u64 w = count * pl[i].group_bytes;
+    HIP_OK(hipMemcpy2DAsync(dst, w, pl[i].base + first * pl[i].group_bytes, pl[i].pitch, w,
+                            pl[i].rows, hipMemcpyDeviceToHost, e->stream));
+    dst += w * pl[i].rows;
+  }
+  HIP_OK(hipStreamSynchronize(e->stream));
+  return RBE_OK;
+}
+
+// The heap section `sec` of a snapshot (checked by ck_heap_check, which filled
+// rec_off) against this engine's heap: CK_SCATTER writes its records at their
+// own positions (resume), CK_COMPARE answers RBE_E_STATE unless every record
+// is valid here and byte-equal to the heap's (hand-off).  One upload of the
+// section, one of the offsets, one kernel.
+static int ck_import_heap(rbe_engine* e, const u8* sec, u64 sec_bytes, const std::vector<u64>& rec_off,
+                          int mode) {
+  const u64 n_rec = rec_off.size() - 1, units = rec_off[n_rec];
+  const u64 o_recs = sizeof(SnapHeapHdr) + n_rec * sizeof(SnapHeapRow);
+  const HostHeap& hp = e->hin.heap;
+  int rc;
+  if (mode == CK_COMPARE) {
+    for (u64 i = 0; i < n_rec; i++) {
+      SnapHeapRow x;
+      memcpy(&x, sec + sizeof(SnapHeapHdr) + i * sizeof(x), sizeof(x));
+      if (!hp.valid(x.pos, (u64)kHeapHdr + x.len)) return RBE_E_STATE;
+    }
+    if ((rc = heap_upload_staged(e))) return rc;
+  }
+  if (!units) return RBE_OK;
+  // error word | the section | the record offsets
+  const u64 o_sec = 256, o_off = o_sec + ((sec_bytes + 255) & ~255ull);
+  if ((rc = grow(&e->ck_sec, &e->ck_sec_bytes, o_off + (n_rec + 1) * sizeof(u64), false))) return rc;
+  u8* d = e->ck_sec;
+  HIP_OK(hipMemsetAsync(d, 0, sizeof(u32), e->stream));
+  HIP_OK(hipMemcpyAsync(d + o_sec, sec, sec_bytes, hipMemcpyHostToDevice, e->stream));
+  HIP_OK(hipMemcpyAsync(d + o_off, rec_off.data(), (n_rec + 1) * sizeof(u64), hipMemcpyHostToDevice,
+                        e->stream));
+  const dim3 g(std::min(grid_for(units), kCkRecGrid));
+  const SnapHeapRow* rows = (const SnapHeapRow*)(d + o_sec + sizeof(SnapHeapHdr));
+  if (mode == CK_SCATTER)
+    hipLaunchKernelGGL(k_ck_records<CK_SCATTER>, g, dim3(kBlock), 0, e->stream, e->heap,
+                       (u64)e->C.heap_bytes, rows, (const u64*)(d + o_off), n_rec,
+                       d + o_sec + o_recs, units, (u32*)d);
+  else
+    hipLaunchKernelGGL(k_ck_records<CK_COMPARE>, g, dim3(kBlock), 0, e->stream, e->heap,
+                       (u64)e->C.heap_bytes, rows, (const u64*)(d + o_off), n_rec,
+                       d + o_sec + o_recs, units, (u32*)d);
+  HIP_OK(hipGetLastError());
+  u32 herr = 0;
+  HIP_OK(hipMemcpyAsync(&herr, d, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  return herr ? RBE_E_STATE : RBE_OK;
+}
+
 extern "C" {
+
+int rbe_export_groups_ex(rbe_engine* e, uint64_t first, uint64_t count, uint32_t flags, void* buf,
+                         uint64_t cap, uint64_t* bytes) {
+  if (!e || !bytes || count == 0 || first >= e->C.n_groups || count > e->C.n_groups - first ||
+      (flags & ~RBE_EXPORT_HEAP))
+    return RBE_E_INVALID;
+  return ck_export(e, first, count, (flags & RBE_EXPORT_HEAP) != 0, buf, cap, bytes);
+}
 
 int rbe_export_bytes(rbe_engine* e, uint64_t first, uint64_t count, uint64_t* bytes) {
   if (!e || !bytes || count == 0 || first >= e->C.n_groups || count > e->C.n_groups - first)
@@ -1231,6 +1463,27 @@ int rbe_import_groups(rbe_engine* e, const void* buf, uint64_t bytes, uint32_t f
   std::vector<u64> rec_off(nr);
   if (snap_log_index(e->C, (const u8*)buf, nr, rec_off.data())) return RBE_E_INVALID;
   HIP_OK(hipSetDevice(e->device));
+  // A heap section after the log section (rbe_checkpoint.h) is checked whole,
+  // and at a hand-off compared with this engine's heap, before anything
+  // changes; trailing bytes without its magic are ignored.
+  const u64 hs_at = snap_log_at(h.body_bytes) + h.log_bytes;
+  const u8* hsec = (const u8*)buf + hs_at;
+  const bool has_heap = ck_heap_present(hsec, bytes - hs_at);
+  std::vector<u64> heap_off;
+  SnapHeapHdr hh = {};
+  u64 heap_sec_bytes = 0;
+  if (has_heap) {
+    memcpy(&hh, hsec, sizeof(hh));
+    if (hh.n_records > (bytes - hs_at) / sizeof(SnapHeapRow)) return RBE_E_INVALID;
+    heap_off.resize(hh.n_records + 1);
+    if (ck_heap_check(e->C.heap_bytes, hsec, bytes - hs_at, &heap_sec_bytes, heap_off.data()))
+      return RBE_E_INVALID;
+    if (resume && !e->hin.empty()) return RBE_E_STATE;  // inputs staged since the last step
+    if (!resume) {
+      const int rc = ck_import_heap(e, hsec, heap_sec_bytes, heap_off, CK_COMPARE);
+      if (rc) return rc;
+    }
+  }
   // the range's pages go back to the pool before its planes are replaced
   const u32 spar = e->round & 1u;
   hipLaunchKernelGGL(k_spill_release, dim3(grid_for(nr)), dim3(kBlock), 0, e->stream, e->P, e->C,
@@ -1275,6 +1528,20 @@ int rbe_import_groups(rbe_engine* e, const void* buf, uint64_t bytes, uint32_t f
   // imported groups start awake (group sleep, rbe_step.h); the next round
   // scans every group to rebuild the awake list and the sleeping totals
   HIP_OK(hipMemsetAsync(e->P.gwake + h.first, GW_AWAKE, h.count, e->stream));
+  if (resume && has_heap) {
+    // the records at their own positions; the host's view of the heap restarts
+    // at the section's head with nothing staged and the live mark unknown
+    const int rc = ck_import_heap(e, hsec, heap_sec_bytes, heap_off, CK_SCATTER);
+    if (rc) return rc;
+    HostHeap& hp = e->hin.heap;
+    hp.stage.clear();
+    hp.head = hp.flushed = hp.batch_lo = hh.head;
+    hp.round_lo = ~0ull;
+    hp.live_lo = 0;
+    e->heap_head_host = hh.head;
+    HIP_OK(hipMemcpyAsync(e->heap_dev, &e->heap_head_host, sizeof(u64), hipMemcpyHostToDevice,
+                          e->stream));
+  }
   if (resume) {
     // the whole engine moves to the snapshot's round; the work lists of the
     // coming round start empty, as after any round (k_triage clears them)
@@ -1338,6 +1605,9 @@ int rbe_destroy(rbe_engine* e) {
   if (e->ce_s2) HIP_IGNORE(hipFree(e->ce_s2));
   if (e->ce_meta) HIP_IGNORE(hipFree(e->ce_meta));
   if (e->ce_cmd) HIP_IGNORE(hipFree(e->ce_cmd));
+  for (u8* p : {e->ck_s, e->ck_list, e->ck_log, e->ck_ref, e->ck_sec})
+    if (p) HIP_IGNORE(hipFree(p));
+  if (e->ck_host) HIP_IGNORE(hipHostFree(e->ck_host));
   for (int i = 0; i < 3; i++)
     if (e->ce_host[i]) HIP_IGNORE(hipHostFree(e->ce_host[i]));
   if (e->wire_dev) HIP_IGNORE(hipFree(e->wire_dev));

@@ -230,7 +230,7 @@ EXPORTS = ["rbe_create", "rbe_destroy", "rbe_abi_version", "rbe_abi_sizes", "rbe
            "rbe_spill_stats", "rbe_cold_tier_stats",
            "rbe_footprint", "rbe_profile_rounds", "rbe_get_kernel_counters", "rbe_kernel_name",
            "rbe_xchg_record_bytes", "rbe_xchg_pack", "rbe_xchg_unpack", "rbe_get_outbox",
-           "rbe_push_messages", "rbe_snapshot_bytes", "rbe_export_bytes", "rbe_export_groups", "rbe_import_groups",
+           "rbe_push_messages", "rbe_snapshot_bytes", "rbe_export_bytes", "rbe_export_groups", "rbe_export_groups_ex", "rbe_import_groups",
            "rbe_get_entry_cmds", "rbe_set_apply_ready", "rbe_collect_outputs", "rbe_collect_updates", "rbe_launch",
            "rbe_xchg_chunk_bytes", "rbe_xchg_pack_fixed", "rbe_xchg_unpack_fixed",
            "rbe_xchg_status", "rbe_stream", "rbe_get_snapshot_state", "rbe_wire_encode",
@@ -247,6 +247,7 @@ _lib = None
 
 RBE_E_INVALID, RBE_E_NOMEM, RBE_E_STATE, RBE_E_CORRUPT = -1, -3, -5, -6
 RBE_STEP_NO_TICK = 1
+RBE_EXPORT_HEAP = 1
 
 
 class EngineError(RuntimeError):
@@ -346,6 +347,7 @@ def load_library(path: Optional[str] = None):
         "rbe_snapshot_bytes": (i32, [vp, u64, P(u64)]),
         "rbe_export_bytes": (i32, [vp, u64, u64, P(u64)]),
         "rbe_export_groups": (i32, [vp, u64, u64, vp, u64]),
+        "rbe_export_groups_ex": (i32, [vp, u64, u64, u32, vp, u64, P(u64)]),
         "rbe_import_groups": (i32, [vp, vp, u64, u32]),
     }
     ab = path is None and os.environ.get("RBE_LIB")  # an older A/B build may lack newer calls
@@ -432,6 +434,24 @@ class SnapshotError(EngineError):
 def _check(rc: int, what: str):
     if rc != 0:
         raise EngineError(f"{what} failed with rc={rc}")
+
+
+def export_ex_call(fn, h, first: int, count: int, flags: int, cap: Optional[int] = None) -> bytes:
+    """rbe_export_groups_ex: a sizing call, then a filling call (or one call
+    into `cap` bytes)."""
+    nb = C.c_uint64()
+    if cap is None:
+        rc = fn(h, first, count, flags, None, 0, C.byref(nb))
+        if rc not in (0, RBE_E_NOMEM):
+            raise SnapshotError(rc, "rbe_export_groups_ex")
+        cap = nb.value
+    buf = C.create_string_buffer(max(1, cap))
+    rc = fn(h, first, count, flags, buf, cap, C.byref(nb))
+    if rc != 0:
+        e = SnapshotError(rc, "rbe_export_groups_ex")
+        e.bytes_needed = nb.value
+        raise e
+    return buf.raw[:nb.value]
 
 
 def global_groups_call(fn, h, n_groups: int):
@@ -787,10 +807,17 @@ class Engine(NodeInputs):
         return n.value
 
     def export_groups(self, first: int = 0, count: Optional[int] = None,
-                      cap: Optional[int] = None) -> bytes:
+                      cap: Optional[int] = None, heap: bool = False,
+                      device: bool = False) -> bytes:
         """The protocol state of groups [first, first + count) after the last
-        queued round, as bytes (peer.go:64-87 / raft.go:283-330 restated)."""
+        queued round, as bytes (peer.go:64-87 / raft.go:283-330 restated).
+        `heap` appends the payload-heap records the range refers to (a
+        self-contained checkpoint, RBE_EXPORT_HEAP); `device` (implied by
+        `heap`) gathers the log section on the device (rbe_export_groups_ex)."""
         count = self.n_groups - first if count is None else count
+        if heap or device:
+            return export_ex_call(self.lib.rbe_export_groups_ex, self.h, first, count,
+                                  RBE_EXPORT_HEAP if heap else 0, cap)
         if cap is None:
             nb = C.c_uint64()
             _check(self.lib.rbe_export_bytes(self.h, first, count, C.byref(nb)), "rbe_export_bytes")

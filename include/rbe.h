@@ -942,11 +942,40 @@ int rbe_push_messages(rbe_engine* e, uint64_t n, const uint64_t* group, const rb
  *     otherwise), unless flags has RBE_IMPORT_RESUME and the snapshot covers every
  *     group: then the engine resumes at that round.  RBE_E_INVALID when the geometry
  *     (n, ring, capacities) differs or the log section does not match the planes;
- *     RBE_E_NOMEM when the page pool cannot take the log section. */
+ *     RBE_E_NOMEM when the page pool cannot take the log section.
+ *   rbe_export_groups_ex: rbe_export_bytes and rbe_export_groups in one call, with the
+ *     log section gathered on the device (a fixed number of launches, copies and waits,
+ *     whatever the number of pages).  *bytes is always set to the size needed; buf ==
+ *     NULL or a short cap returns RBE_E_NOMEM and writes nothing, so a sizing call and a
+ *     filling call do.  With flags == 0 the bytes are those of rbe_export_groups on the
+ *     same state, refused in the same cases.  With RBE_EXPORT_HEAP and a payload heap
+ *     (cfg.heap_bytes) a heap section follows the log section
+ *     (dragonboat_amd/csrc/rbe_checkpoint.h): every heap record, once, that a log entry
+ *     the range's replicas hold (ring, cold log pages of either tier) or an entry of a
+ *     message the next round reads refers to and that is still readable (a lapped
+ *     record stays RBE_E_STATE for readers after a resume as before); records still
+ *     staged for the next step are uploaded first.  Inputs pushed since the last step are
+ *     not part of a snapshot.  RBE_E_STATE also when two references to one heap position
+ *     disagree on the record's length.
+ *   A heap section makes the checkpoint self-contained: rbe_import_groups recognises it
+ *     after the log section and checks it whole before it changes anything (RBE_E_INVALID
+ *     for a table that is not strictly ascending, an unaligned position, a record across
+ *     the ring end, past the section's head or more than a lap below it, overlapping
+ *     records, a size mismatch, or a heap size that is not this engine's).  With
+ *     RBE_IMPORT_RESUME the records are written at their own positions and the heap's
+ *     head moves to the section's, so a fresh engine reads every carried Cmd back
+ *     (RBE_E_STATE when inputs have been staged since the engine's last step).  Without
+ *     it (a hand-off at the same round) the section is only verified: every record must
+ *     be valid in this engine's heap and byte-equal to what is there, RBE_E_STATE
+ *     otherwise, with nothing changed.  Moving records to new positions in another
+ *     engine's heap is not supported. */
 #define RBE_IMPORT_RESUME 0x1u
+#define RBE_EXPORT_HEAP 0x1u
 int rbe_snapshot_bytes(rbe_engine* e, uint64_t count, uint64_t* bytes);
 int rbe_export_bytes(rbe_engine* e, uint64_t first, uint64_t count, uint64_t* bytes);
 int rbe_export_groups(rbe_engine* e, uint64_t first, uint64_t count, void* buf, uint64_t cap);
+int rbe_export_groups_ex(rbe_engine* e, uint64_t first, uint64_t count, uint32_t flags,
+                         void* buf, uint64_t cap, uint64_t* bytes);
 int rbe_import_groups(rbe_engine* e, const void* buf, uint64_t bytes, uint32_t flags);
 
 /* Device memory footprint (bytes) of a configuration, without allocating. */
