@@ -19,6 +19,7 @@
 #include "../../include/rbe.h"
 #include "rbe_host.h"
 #include "rbe_kernels.h"
+#include "rbe_launch_kernels.h"
 #include "rbe_snap.h"
 #include "rbe_wire_kernels.h"
 
@@ -463,24 +464,8 @@ __global__ __launch_bounds__(kBlock) void k_upd_write(Planes P, u32 n, u64 first
   ou[at] = u;
 }
 
-// rbe_launch: one lane per relaunched replica (rbe_step.h relaunch_replica)
-struct LaunchRec {
-  u64 replica, term, vote, commit, last, off;  // off: first row in the terms/bodies arrays
-  u32 n, removed;                              // removed: rbe_launch_state::removed
-  u64 marker, marker_term, ss_index, ss_term;  // compacted LogDB (rbe_launch_state)
-};
-template <int N>
-__global__ __launch_bounds__(kBlock) void k_relaunch(Planes P, Params C, const LaunchRec* rec,
-                                                     u64 n, const u64* terms, const Body* bodies,
-                                                     u32 ppar, u32 tclk) {
-  const u64 i = (u64)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const LaunchRec x = rec[i];
-  relaunch_replica<N>(P, C, x.replica, x.term, x.vote, x.commit, x.last, x.n, terms + x.off,
-                      bodies + x.off, ppar, tclk, x.marker, x.marker_term, x.ss_index, x.ss_term,
-                      x.removed);
-  P.gwake[x.replica / N] = GW_AWAKE;
-}
+// rbe_launch: k_relaunch and the passes that build the launched cold logs are
+// in rbe_launch_kernels.h
 
 // rbe_replace_node: whether slot (replica % N) is still referenced in its
 // group (rbe_step.h slot_referenced), then the new node in the slot
@@ -2221,23 +2206,49 @@ int rbe_launch(rbe_engine* e, uint64_t n, const uint64_t* replica, const rbe_lau
                        st[i].marker_term, st[i].snapshot_index, st[i].snapshot_term};
     off += st[i].n_entries;
   }
+  // the cold part of the LogDBs, planned on the host (rbe_launch.h): without
+  // one (no launched replica has an entry below its ring) k_relaunch alone
+  std::vector<LaunchPg> pg;
+  std::vector<u32> page_off;
+  const u64 np = launch_plan(e->C, n, st, bodies.data(), pg, page_off);
+  if (np > 0xFFFFFFF0ull) return RBE_E_NOMEM;  // (page ids are u32)
   const u64 b_rec = n * sizeof(LaunchRec), b_t = terms.size() * sizeof(u64);
-  const u64 bytes = b_rec + b_t + bodies.size() * sizeof(Body) + 64;
+  const u64 b_b = bodies.size() * sizeof(Body);
+  const u64 b_pg = np ? n * sizeof(LaunchPg) : 0, b_po = np ? (n + 1) * sizeof(u32) : 0;
+  const u64 bytes = b_rec + b_t + b_b + b_pg + b_po + np * sizeof(u32) + 64;
   rc = grow(&e->gat_dev, &e->gat_dev_bytes, bytes, false);  // (engine scratch, as rbe_replace_node)
   if (rc) return rc;
   u8* d = e->gat_dev;
+  const LaunchRec* d_rec = (const LaunchRec*)d;
+  const u64* d_t = (const u64*)(d + b_rec);
+  const Body* d_b = (const Body*)(d + b_rec + b_t);
+  const LaunchPg* d_pg = np ? (const LaunchPg*)(d + b_rec + b_t + b_b) : nullptr;
+  const u32* d_po = np ? (const u32*)(d + b_rec + b_t + b_b + b_pg) : nullptr;
+  u32* d_ids = np ? (u32*)(d + b_rec + b_t + b_b + b_pg + b_po) : nullptr;
   HIP_OK(hipMemcpyAsync(d, rec.data(), b_rec, hipMemcpyHostToDevice, e->stream));
   if (b_t) {
-    HIP_OK(hipMemcpyAsync(d + b_rec, terms.data(), b_t, hipMemcpyHostToDevice, e->stream));
-    HIP_OK(hipMemcpyAsync(d + b_rec + b_t, bodies.data(), bodies.size() * sizeof(Body),
-                          hipMemcpyHostToDevice, e->stream));
+    HIP_OK(hipMemcpyAsync((void*)d_t, terms.data(), b_t, hipMemcpyHostToDevice, e->stream));
+    HIP_OK(hipMemcpyAsync((void*)d_b, bodies.data(), b_b, hipMemcpyHostToDevice, e->stream));
   }
   const u32 ppar = (e->round & 1u) ^ 1u;
+  if (np) {
+    // release, then an id per page, then the pages a wave each; the grids are
+    // fixed, so the launch count does not depend on the page count
+    HIP_OK(hipMemcpyAsync((void*)d_pg, pg.data(), b_pg, hipMemcpyHostToDevice, e->stream));
+    HIP_OK(hipMemcpyAsync((void*)d_po, page_off.data(), b_po, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_launch_release, dim3(grid_for(n)), dim3(kBlock), 0, e->stream, e->P,
+                       e->C, d_rec, (u64)n, ppar ^ 1u);
+    hipLaunchKernelGGL(k_launch_alloc, dim3(std::min(grid_for(np), kLaunchAllocGrid)),
+                       dim3(kBlock), 0, e->stream, e->P, e->C, d_po, (u64)n, d_ids);
+    hipLaunchKernelGGL(k_launch_fill, dim3(std::min(grid_for(np * 64), kLaunchFillGrid)),
+                       dim3(kBlock), 0, e->stream, e->P, d_pg, d_po, (u64)n, d_t, d_b,
+                       (const u32*)d_ids);
+    HIP_OK(hipGetLastError());
+  }
   rc = dispatch_n(e->C.n, [&](auto NN) {
     constexpr int N = decltype(NN)::value;
     hipLaunchKernelGGL(k_relaunch<N>, dim3(grid_for(n)), dim3(kBlock), 0, e->stream, e->P, e->C,
-                       (const LaunchRec*)d, (u64)n, (const u64*)(d + b_rec),
-                       (const Body*)(d + b_rec + b_t), ppar, e->tclk);
+                       d_rec, (u64)n, d_t, d_b, ppar, e->tclk, d_pg, d_po, (const u32*)d_ids);
     HIP_OK(hipGetLastError());
     return RBE_OK;
   });

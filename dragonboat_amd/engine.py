@@ -642,7 +642,11 @@ class NodeInputs:
         not list as a voter) and
         entries[i] = [(index, term, type, cmd[, key, client_id, series_id,
         responded_to]), ...], the tail of its LogDB (Peer.Launch over an
-        existing log, peer.go:64-86)."""
+        existing log, peer.go:64-86).  The entries below the ring go to the cold
+        log a page at a time: the launch reuses the pages it releases, puts
+        every page but a replica's last into the host tier when there is one
+        (host_pool_bytes), and a replica that finds both tiers full faults
+        alone with F_NOMEM and an empty cold log."""
         n = len(replicas)
         st = (RbeLaunchState * max(1, n))()
         flat = []

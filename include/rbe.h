@@ -339,7 +339,16 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out);
  * st[i].n_entries entries of `ents`: the LogDB's entries above its marker,
  * up to last_index (the ring takes the newest cfg.ring of them, the cold log
  * the rest; a LogDB handed over only in part faults with RBE_FAULT_WINDOW when
- * the replica later needs an entry below what it was given).  The
+ * the replica later needs an entry below what it was given).  The cold part
+ * is built a page at a time from a plan made on the host: the replicas' old
+ * chains and pooled ReadIndex queues are released first and the new pages may
+ * take what was released, so a launch into a running engine needs no more
+ * pool than the logs it leaves behind.  With cfg.host_pool_bytes every cold
+ * page but a replica's last goes to a page of the host tier (an HBM page when
+ * the tier is full), so a tiered engine restarts whatever the size of its HBM
+ * pool.  A replica one of whose pages finds no room in either tier takes
+ * RBE_FAULT_NOMEM alone, with an empty cold log and none of its pages kept;
+ * the rest of the batch is launched as usual.  The
  * entries' Cmds are concatenated in `cmd` (null: each is its rbe_entry.cmd,
  * at most 16 bytes); entries with longer Cmds or session fields go to the
  * payload heap.  Checked whole before anything changes (RBE_E_INVALID;
