@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -20,6 +21,7 @@
 #include "rbe_host.h"
 #include "rbe_kernels.h"
 #include "rbe_launch_kernels.h"
+#include "rbe_scratch.h"
 #include "rbe_snap.h"
 #include "rbe_wire_kernels.h"
 
@@ -728,15 +730,28 @@ static int abi_nomem(F&& f) {
 }
 
 struct rbe_engine {
+  // the stream is declared first, so it is destroyed last: after every buffer
+  // below has been released (~rbe_engine)
+  struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() {
+      if (s) HIP_IGNORE(hipStreamDestroy(s));
+    }
+    operator hipStream_t() const { return s; }
+  } stream;
   rbe_config cfg;
   Params C;
   Planes P;
   int device = 0;
-  hipStream_t stream = nullptr;
   u32 round = 0;
   u32 tclk = 0;              // ticks before the next round (Clk::tclk)
   u32* d_clk = nullptr;      // device copy {round, tclk} read by graph replays
-  std::vector<void*> allocs;
+  // fixed device allocations (dev_fixed): the planes, lists, heap, counters.
+  // Planes and Lists hold raw pointers into them, as kernels take both by value
+  std::vector<Scratch<DevMem>> fixed;
   // captured K-round graphs, one per round count K (rbe_run; rbe_prepare_run
   // captures ahead of a timed region), replaced round-robin
   static constexpr int kGraphs = 4;
@@ -756,10 +771,8 @@ struct rbe_engine {
   HostInputsT<PinnedAlloc>::UpVec<ExtIn> up_recs;
   HostInputsT<PinnedAlloc>::UpVec<Ent> up_ents;
   u64 in_used = 0;
-  u8* in_pinned[2] = {nullptr, nullptr};  // pinned staging of the small input parts, by
-  u64 in_pbytes[2] = {0, 0};              // flush parity, and their capacities
-  u8* in_dev = nullptr;      // the device copy (replicas, records, applied pairs, ...)
-  u64 in_bytes = 0;
+  Scratch<PinnedMem> in_pinned[2];  // pinned staging of the small input parts, by flush parity
+  Scratch<DevMem> in_dev;    // the device copy (replicas, records, applied pairs, ...)
   hipEvent_t in_ev[2] = {nullptr, nullptr};  // the uploads of flush parity 0 / 1 have finished
   u32 in_slot = 0;
   u8* heap = nullptr;        // payload heap (cfg.heap_bytes; positions in hin.heap)
@@ -768,52 +781,36 @@ struct rbe_engine {
   u64 heap_head_host = 0;    // source of [0]
   u32 scan_at = 0;           // host copy of Lists::scan_round (the source of its upload)
   // rbe_collect_outputs: device scratch and the pinned host copy it returns
-  u8* out_dev = nullptr;
-  u64 out_dev_bytes = 0;
-  u8* gat_dev = nullptr;  // rbe_get_entries' gather buffer (k_log_gather)
-  u64 gat_dev_bytes = 0;
+  Scratch<DevMem> out_dev;
+  Scratch<PinnedMem> out_host;
+  Scratch<DevMem> gat_dev;  // rbe_get_entries' gather buffer (k_log_gather)
   // the cold log's host tier (cfg.host_pool_bytes): the arena behind
   // SpillCtl::hpool, and the demotion's move list (k_cold_demote_plan)
-  Ent* hpool_host = nullptr;
+  Scratch<MappedMem> hpool_host;
   SpillCtl tier_init;  // the source of the tier constants' upload (rbe_create)
-  ColdMove* cmove = nullptr;
+  Scratch<DevMem> cmove;
   u32 cmove_cap = 0;
-  u8* out_host = nullptr;
-  u64 out_host_bytes = 0;
   // replica mode with the isolation schedule: every rank's leader bits, ORed
   // by the host, for the epoch round iso_round (rbe_set_iso_leaders)
-  u8* iso_dev = nullptr;
+  Scratch<DevMem> iso_dev;
   u32 iso_round = ~0u;
   // rbe_wire_ingest scratch (keys, indexes, heap offsets, sort temporary)
-  u8* ing_dev = nullptr;
-  u64 ing_dev_bytes = 0;
+  Scratch<DevMem> ing_dev;
   // capacities the no-read-back ingest launches for (messages, entries, Cmd
   // bytes): the last call's counts + 25%; 0 until a call has measured them
   u64 ing_cap[3] = {0, 0, 0};
   // rbe_collect_updates: the same for the compacted Updates
-  u8* upd_dev = nullptr;
-  u64 upd_dev_bytes = 0;
-  u8* upd_host = nullptr;
-  u64 upd_host_bytes = 0;
+  Scratch<DevMem> upd_dev;
+  Scratch<PinnedMem> upd_host;
   // rbe_collect_step: the same for Updates + their outputs
-  u8* cs_dev = nullptr;
-  u64 cs_dev_bytes = 0;
-  u8* cs_host = nullptr;
-  u64 cs_host_bytes = 0;
+  Scratch<DevMem> cs_dev;
+  Scratch<PinnedMem> cs_host;
   // rbe_collect_entries / rbe_collect_entry_ranges (ce_collect): device scratch
   // sized by the ranges (s1) and by the entries (s2), the device lists (meta:
   // replicas, offsets, records; cmd: the Cmd bytes), and one pinned host copy
   // per source: EntriesToSave, CommittedEntries, host-named ranges
-  u8* ce_s1 = nullptr;
-  u64 ce_s1_bytes = 0;
-  u8* ce_s2 = nullptr;
-  u64 ce_s2_bytes = 0;
-  u8* ce_meta = nullptr;
-  u64 ce_meta_bytes = 0;
-  u8* ce_cmd = nullptr;
-  u64 ce_cmd_bytes = 0;
-  u8* ce_host[3] = {nullptr, nullptr, nullptr};
-  u64 ce_host_bytes[3] = {0, 0, 0};
+  Scratch<DevMem> ce_s1, ce_s2, ce_meta, ce_cmd;
+  Scratch<PinnedMem> ce_host[3];
   // whether k_ce_entries stages a block's records in LDS (RBE_COLLECT_STAGE=0:
   // every lane stores its own)
   bool ce_stage = true;
@@ -821,46 +818,40 @@ struct rbe_engine {
   // ck_import_heap): scratch sized by the replicas (s), the flat page list, the
   // gathered log section, the reference pairs with their sort and scan scratch,
   // the heap section, and the pinned host copy of both sections
-  u8* ck_s = nullptr;
-  u64 ck_s_bytes = 0;
-  u8* ck_list = nullptr;
-  u64 ck_list_bytes = 0;
-  u8* ck_log = nullptr;
-  u64 ck_log_bytes = 0;
-  u8* ck_ref = nullptr;
-  u64 ck_ref_bytes = 0;
-  u8* ck_sec = nullptr;
-  u64 ck_sec_bytes = 0;
-  u8* ck_host = nullptr;
-  u64 ck_host_bytes = 0;
+  Scratch<DevMem> ck_s, ck_list, ck_log, ck_ref, ck_sec;
+  Scratch<PinnedMem> ck_host;
   // rbe_collect_step_begin / _end: mapped host memory the write kernel fills
   // directly (header | replicas | updates | offsets | messages | ReadyToReads),
   // its capacities, the pending call and its completion event
-  u8* csa_buf[2] = {nullptr, nullptr};  // two, used in turn: a round's records
-  u64 csa_bytes[2] = {0, 0};              // outlive the next round's _begin
-  u32 csa_slot = 0;
-  u8* csa_host = nullptr;                 // the slot of the pending / last call
+  Scratch<MappedMem> csa_buf[2];  // two, used in turn: a round's records
+  u32 csa_slot = 0;               // outlive the next round's _begin
+  u8* csa_host = nullptr;         // the slot of the pending / last call (not owned)
   u64 csa_cap[3] = {0, 0, 0};
   bool csa_pending = false;
   u64 csa_first = 0, csa_count = 0;
   u32 csa_flags = 0, csa_round = 0;
   hipEvent_t csa_ev = nullptr;
   // rbe_wire_encode / rbe_wire_decode scratch
-  u8* wire_dev = nullptr;    // the last rbe_wire_encode's frames (rbe_wire_fetch)
-  u64 wire_dev_bytes = 0;
-  u8* wire_meta = nullptr;   // cells, batches, frame index
-  u64 wire_meta_bytes = 0;
-  u8* wire_rec = nullptr;    // decoded records
-  u64 wire_rec_bytes = 0;
-  u8* wire_in = nullptr;     // rbe_wire_decode: inbound bytes and per-frame scratch
-  u64 wire_in_bytes = 0;
-  u8* wire_big_buf = nullptr;  // the chunked walk of big frames: exits, counts, chunk lists
-  u64 wire_big_bytes = 0;
+  Scratch<DevMem> wire_dev;    // the last rbe_wire_encode's frames (rbe_wire_fetch)
+  Scratch<DevMem> wire_meta;   // cells, batches, frame index
+  Scratch<DevMem> wire_rec;    // decoded records
+  Scratch<DevMem> wire_in;     // rbe_wire_decode: inbound bytes and per-frame scratch
+  Scratch<DevMem> wire_big_buf;  // the chunked walk of big frames: exits, counts, chunk lists
   // frames longer than this are walked by chunks (k_wire_chunk_exit / hop /
   // emit), shorter ones by one block each (k_wire_bounds); RBE_WIRE_BIG sets it
   u64 wire_big = 256u << 10;
   u64 wire_totals[4] = {0, 0, 0, 0};
   u64 wire_frames_off = 0;   // frame index inside wire_meta
+
+  rbe_engine() = default;
+  // the caller has made `device` current (rbe_destroy; rbe_create's guard)
+  ~rbe_engine() {
+    if (stream) HIP_IGNORE(hipStreamSynchronize(stream));
+    for (hipGraphExec_t g : graph)
+      if (g) HIP_IGNORE(hipGraphExecDestroy(g));
+    for (hipEvent_t ev : {ev0, ev1, in_ev[0], in_ev[1], csa_ev})
+      if (ev) HIP_IGNORE(hipEventDestroy(ev));
+  }
 };
 
 unsigned rbe::g_fast_grid = rbe::kFastGrid;
@@ -886,10 +877,29 @@ static int read_heap(rbe_engine* e, u64 pos, u64 off, u64 len, u8* dst) {
   return RBE_OK;
 }
 
+// `bytes` of device memory the engine owns until it is destroyed, zero-filled
+// on the stream with `zero`.  The pointer stays raw: it goes into Planes or
+// Lists, which kernels take by value.
+template <class T>
+static int dev_fixed(rbe_engine* e, T** out, u64 bytes, bool zero = false) {
+  Scratch<DevMem> b;
+  if (b.reserve_cap(bytes, bytes)) return RBE_E_NOMEM;
+  if (zero && hipMemsetAsync(b.p(), 0, bytes, e->stream) != hipSuccess) return RBE_E_HIP;
+  *out = (T*)b.p();
+  e->fixed.push_back(std::move(b));
+  return RBE_OK;
+}
+// the node id table, allocated by the first call that sets an id
+static int node_ids_alloc(rbe_engine* e, u64 bytes) {
+  if (e->P.node_ids) return RBE_OK;
+  u64* d = nullptr;
+  const int rc = dev_fixed(e, &d, bytes);
+  e->P.node_ids = d;
+  return rc;
+}
 
 static int read_window(rbe_engine* e, u64 replica, u64 lo, u64 hi, std::vector<u64>& t,
                        std::vector<Body>& b);
-static int grow(u8** p, u64* have, u64 need, bool pinned);
 static int host_list(rbe_engine* e, u32 par, u64 li, u32 w, const Msg* pl, std::vector<Msg>& out);
 
 static constexpr int kPlaneAllocs = 30;
@@ -1063,9 +1073,9 @@ static int launch_step(rbe_engine* e, RoundArg ra,
   // (no new branch, so a K-round graph captures the two like the rest)
   const unsigned gp = std::min(grid_for(e->C.n_rep), kPlanGrid);
   hipLaunchKernelGGL(k_cold_demote_plan, dim3(gp), dim3(kBlock), 0, e->stream,
-                     e->P, e->C, ra, e->cmove, e->cmove_cap);
+                     e->P, e->C, ra, (ColdMove*)e->cmove.p(), e->cmove_cap);
   hipLaunchKernelGGL(k_cold_demote_copy, dim3(kDemoteGrid), dim3(kBlock), 0, e->stream, e->P, ra,
-                     (const ColdMove*)e->cmove, e->cmove_cap, e->C.host_pages);
+                     (const ColdMove*)e->cmove.p(), e->cmove_cap, e->C.host_pages);
   return hipGetLastError() == hipSuccess ? RBE_OK : RBE_E_HIP;
 }
 
@@ -1140,7 +1150,8 @@ struct SnapLogDev {
   }
   void page(u32 p, Ent* out) {
     if (e->C.host_pages && p >= e->C.pool_pages) {  // (the stream was synchronised: read in place)
-      memcpy(out, e->hpool_host + (u64)(p - e->C.pool_pages) * kPageEnts, kPageEnts * sizeof(Ent));
+      memcpy(out, (const Ent*)e->hpool_host.p() + (u64)(p - e->C.pool_pages) * kPageEnts,
+             kPageEnts * sizeof(Ent));
       return;
     }
     if (hipMemcpy(out, e->P.pool + (u64)p * kPageEnts, kPageEnts * sizeof(Ent),
@@ -1212,13 +1223,13 @@ static int ck_export(rbe_engine* e, u64 first, u64 count, bool want_heap, void* 
   // scratch: error word | reference counter | block sums (pairs) | block prefixes (+ totals)
   const u32 nb = grid_for(nr);
   const u64 o_cnt = 256, o_bs = 512, o_pre = o_bs + al(2ull * nb * sizeof(u32));
-  if ((rc = grow(&e->ck_s, &e->ck_s_bytes, o_pre + al(scan_words(2, nb) * sizeof(u64)), false)))
+  if ((rc = e->ck_s.reserve(o_pre + al(scan_words(2, nb) * sizeof(u64)))))
     return rc;
-  u32* err = (u32*)e->ck_s;
-  unsigned long long* cnt = (unsigned long long*)(e->ck_s + o_cnt);
-  u32* bsum = (u32*)(e->ck_s + o_bs);
-  u64* pre = (u64*)(e->ck_s + o_pre);
-  HIP_OK(hipMemsetAsync(e->ck_s, 0, 512, e->stream));
+  u32* err = (u32*)e->ck_s.p();
+  unsigned long long* cnt = (unsigned long long*)(e->ck_s.p() + o_cnt);
+  u32* bsum = (u32*)(e->ck_s.p() + o_bs);
+  u64* pre = (u64*)(e->ck_s.p() + o_pre);
+  HIP_OK(hipMemsetAsync(e->ck_s.p(), 0, 512, e->stream));
   hipLaunchKernelGGL(k_ck_count, dim3(nb), dim3(kBlock), 0, e->stream, e->P, C, r0, nr, bsum);
   if ((rc = launch_scan<2>(e->stream, bsum, nb, pre))) return rc;
   u64 tot[2];
@@ -1226,16 +1237,16 @@ static int ck_export(rbe_engine* e, u64 first, u64 count, bool want_heap, void* 
   HIP_OK(hipMemcpyAsync(tot, pre + 2ull * nb, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
   const u64 np = tot[0], lb = tot[1] * 16;
-  if ((rc = grow(&e->ck_list, &e->ck_list_bytes, (np + 1) * sizeof(CkPage), false))) return rc;
-  if ((rc = grow(&e->ck_log, &e->ck_log_bytes, lb + 16, false))) return rc;
-  CkPage* list = (CkPage*)e->ck_list;
+  if ((rc = e->ck_list.reserve((np + 1) * sizeof(CkPage)))) return rc;
+  if ((rc = e->ck_log.reserve(lb + 16))) return rc;
+  CkPage* list = (CkPage*)e->ck_list.p();
   CkCaps caps{np, tot[1], 0};
   hipLaunchKernelGGL(k_ck_replicas, dim3(nb), dim3(kBlock), 0, e->stream, e->P, C, r0, nr,
-                     (const u64*)pre, e->ck_log, list, caps, err);
+                     (const u64*)pre, e->ck_log.p(), list, caps, err);
   if (np)
     hipLaunchKernelGGL(k_ck_pages, dim3(std::min(grid_for(np * 64), kCkPageGrid)), dim3(kBlock), 0,
                        e->stream, e->P, (const u64*)(pre + 2ull * nb), (const CkPage*)list,
-                       e->ck_log, caps);
+                       e->ck_log.p(), caps);
   HIP_OK(hipGetLastError());
   u64 hb = 0;
   if (heap) {
@@ -1243,7 +1254,7 @@ static int ck_export(rbe_engine* e, u64 first, u64 count, bool want_heap, void* 
     const unsigned g = std::min(grid_for(n_all), kCkRefGrid);
     hipLaunchKernelGGL(k_ck_refs<false>, dim3(g), dim3(kBlock), 0, e->stream, e->P, C, r0, nr,
                        e->round, head, (const u64*)(pre + 2ull * nb), (const CkPage*)list,
-                       (const u8*)e->ck_log, (u64*)nullptr, (u32*)nullptr, cnt, caps, err);
+                       (const u8*)e->ck_log.p(), (u64*)nullptr, (u32*)nullptr, cnt, caps, err);
     HIP_OK(hipGetLastError());
     u64 n_ref = 0;
     HIP_OK(hipMemcpyAsync(&n_ref, cnt, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
@@ -1262,8 +1273,8 @@ static int ck_export(rbe_engine* e, u64 first, u64 count, bool want_heap, void* 
     const u64 o_ro = o_sv + al(n_ref * 4), o_bs2 = o_ro + al((n_ref + 1) * 8);
     const u64 o_pre2 = o_bs2 + al(2ull * nb2 * sizeof(u32));
     const u64 o_tmp = o_pre2 + al(scan_words(2, nb2) * sizeof(u64));
-    if ((rc = grow(&e->ck_ref, &e->ck_ref_bytes, o_tmp + al(tb), false))) return rc;
-    u8* b = e->ck_ref;
+    if ((rc = e->ck_ref.reserve(o_tmp + al(tb)))) return rc;
+    u8* b = e->ck_ref.p();
     u64 *keys = (u64*)b, *skeys = (u64*)(b + o_sk), *rec_off = (u64*)(b + o_ro);
     u32 *vals = (u32*)(b + o_v), *svals = (u32*)(b + o_sv), *bsum2 = (u32*)(b + o_bs2);
     u64* pre2 = (u64*)(b + o_pre2);
@@ -1272,7 +1283,7 @@ static int ck_export(rbe_engine* e, u64 first, u64 count, bool want_heap, void* 
       HIP_OK(hipMemsetAsync(cnt, 0, sizeof(u64), e->stream));
       hipLaunchKernelGGL(k_ck_refs<true>, dim3(g), dim3(kBlock), 0, e->stream, e->P, C, r0, nr,
                          e->round, head, (const u64*)(pre + 2ull * nb), (const CkPage*)list,
-                         (const u8*)e->ck_log, keys, vals, cnt, caps, err);
+                         (const u8*)e->ck_log.p(), keys, vals, cnt, caps, err);
       HIP_OK(hipGetLastError());
       if (dev_sort_pairs(b + o_tmp, &tb, keys, skeys, vals, svals, n_ref, bits, e->stream))
         return RBE_E_HIP;
@@ -1288,25 +1299,25 @@ static int ck_export(rbe_engine* e, u64 first, u64 count, bool want_heap, void* 
     const u64 n_rec = rt[0], units = rt[1];
     const u64 o_recs = sizeof(SnapHeapHdr) + n_rec * sizeof(SnapHeapRow);
     hb = o_recs + units * 16;
-    if ((rc = grow(&e->ck_sec, &e->ck_sec_bytes, hb, false))) return rc;
+    if ((rc = e->ck_sec.reserve(hb))) return rc;
     hipLaunchKernelGGL(k_ck_table, dim3(nb2), dim3(kBlock), 0, e->stream, (const u64*)skeys,
                        (const u32*)svals, n_ref, (const u64*)pre2, head, (u64)C.heap_bytes,
-                       e->ck_sec, rec_off, n_rec, err);
+                       e->ck_sec.p(), rec_off, n_rec, err);
     if (units)
       hipLaunchKernelGGL(k_ck_records<CK_GATHER>, dim3(std::min(grid_for(units), kCkRecGrid)),
                          dim3(kBlock), 0, e->stream, e->heap, (u64)C.heap_bytes,
-                         (const SnapHeapRow*)(e->ck_sec + sizeof(SnapHeapHdr)),
-                         (const u64*)rec_off, n_rec, e->ck_sec + o_recs, units, err);
+                         (const SnapHeapRow*)(e->ck_sec.p() + sizeof(SnapHeapHdr)),
+                         (const u64*)rec_off, n_rec, e->ck_sec.p() + o_recs, units, err);
     HIP_OK(hipGetLastError());
   }
   const u64 total = snap_log_at(body) + lb + hb;
   *bytes = total;
   const bool fill = buf && cap >= total;
   if (fill) {
-    if ((rc = grow(&e->ck_host, &e->ck_host_bytes, lb + hb, true))) return rc;
-    if (lb) HIP_OK(hipMemcpyAsync(e->ck_host, e->ck_log, lb, hipMemcpyDeviceToHost, e->stream));
+    if ((rc = e->ck_host.reserve(lb + hb))) return rc;
+    if (lb) HIP_OK(hipMemcpyAsync(e->ck_host.p(), e->ck_log.p(), lb, hipMemcpyDeviceToHost, e->stream));
     if (hb)
-      HIP_OK(hipMemcpyAsync(e->ck_host + lb, e->ck_sec, hb, hipMemcpyDeviceToHost, e->stream));
+      HIP_OK(hipMemcpyAsync(e->ck_host.p() + lb, e->ck_sec.p(), hb, hipMemcpyDeviceToHost, e->stream));
   }
   HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
@@ -1317,7 +1328,7 @@ static int ck_export(rbe_engine* e, u64 first, u64 count, bool want_heap, void* 
   h.log_bytes = lb;
   memcpy(buf, &h, sizeof(h));
   memset((u8*)buf + sizeof(h) + body, 0, snap_log_at(body) - sizeof(h) - body);
-  memcpy((u8*)buf + snap_log_at(body), e->ck_host, lb + hb);
+  memcpy((u8*)buf + snap_log_at(body), e->ck_host.p(), lb + hb);
   SnapPlane pl[kSnapPlanes];
   snap_planes(e->P, C, pl);
   u8* dst = (u8*)buf + sizeof(SnapHeader);
@@ -1353,8 +1364,8 @@ static int ck_import_heap(rbe_engine* e, const u8* sec, u64 sec_bytes, const std
   if (!units) return RBE_OK;
   // error word | the section | the record offsets
   const u64 o_sec = 256, o_off = o_sec + ((sec_bytes + 255) & ~255ull);
-  if ((rc = grow(&e->ck_sec, &e->ck_sec_bytes, o_off + (n_rec + 1) * sizeof(u64), false))) return rc;
-  u8* d = e->ck_sec;
+  if ((rc = e->ck_sec.reserve(o_off + (n_rec + 1) * sizeof(u64)))) return rc;
+  u8* d = e->ck_sec.p();
   HIP_OK(hipMemsetAsync(d, 0, sizeof(u32), e->stream));
   HIP_OK(hipMemcpyAsync(d + o_sec, sec, sec_bytes, hipMemcpyHostToDevice, e->stream));
   HIP_OK(hipMemcpyAsync(d + o_off, rec_off.data(), (n_rec + 1) * sizeof(u64), hipMemcpyHostToDevice,
@@ -1486,11 +1497,11 @@ int rbe_import_groups(rbe_engine* e, const void* buf, uint64_t bytes, uint32_t f
   {  // the cold logs and pool-page readIndex queues of the log section
     // device staging: fault word | record offsets | the section (16-B aligned)
     const u64 lb = h.log_bytes, ob = (nr * sizeof(u64) + 15) & ~15ull;
-    const int rc = grow(&e->gat_dev, &e->gat_dev_bytes, 16 + ob + lb, false);
+    const int rc = e->gat_dev.reserve(16 + ob + lb);
     if (rc) return rc;
-    u32* fault = (u32*)e->gat_dev;
-    u64* d_off = (u64*)(e->gat_dev + 16);
-    u8* d_sec = e->gat_dev + 16 + ob;
+    u32* fault = (u32*)e->gat_dev.p();
+    u64* d_off = (u64*)(e->gat_dev.p() + 16);
+    u8* d_sec = e->gat_dev.p() + 16 + ob;
     HIP_OK(hipMemsetAsync(fault, 0, sizeof(u32), e->stream));
     HIP_OK(hipMemcpyAsync(d_off, rec_off.data(), ob, hipMemcpyHostToDevice, e->stream));
     HIP_OK(hipMemcpyAsync(d_sec, (const u8*)buf + snap_log_at(h.body_bytes), lb,
@@ -1560,48 +1571,7 @@ int rbe_footprint(const rbe_config* cfg, uint64_t* bytes) {
 int rbe_destroy(rbe_engine* e) {
   if (!e) return RBE_OK;
   HIP_IGNORE(hipSetDevice(e->device));
-  if (e->stream) HIP_IGNORE(hipStreamSynchronize(e->stream));
-  drop_graphs(e);
-  for (void* p : e->allocs) HIP_IGNORE(hipFree(p));
-  if (e->d_clk) HIP_IGNORE(hipFree(e->d_clk));
-  if (e->ev0) HIP_IGNORE(hipEventDestroy(e->ev0));
-  if (e->ev1) HIP_IGNORE(hipEventDestroy(e->ev1));
-  for (int i = 0; i < 2; i++) {
-    if (e->in_ev[i]) HIP_IGNORE(hipEventDestroy(e->in_ev[i]));
-    if (e->in_pinned[i]) HIP_IGNORE(hipHostFree(e->in_pinned[i]));
-  }
-  if (e->in_dev) HIP_IGNORE(hipFree(e->in_dev));
-  if (e->out_dev) HIP_IGNORE(hipFree(e->out_dev));
-  if (e->gat_dev) HIP_IGNORE(hipFree(e->gat_dev));
-  if (e->hpool_host) HIP_IGNORE(hipHostFree(e->hpool_host));
-  if (e->cmove) HIP_IGNORE(hipFree(e->cmove));
-  if (e->out_host) HIP_IGNORE(hipHostFree(e->out_host));
-  if (e->upd_dev) HIP_IGNORE(hipFree(e->upd_dev));
-  if (e->ing_dev) HIP_IGNORE(hipFree(e->ing_dev));
-  if (e->iso_dev) HIP_IGNORE(hipFree(e->iso_dev));
-  if (e->upd_host) HIP_IGNORE(hipHostFree(e->upd_host));
-  if (e->cs_dev) HIP_IGNORE(hipFree(e->cs_dev));
-  if (e->P.prof) HIP_IGNORE(hipFree(e->P.prof));
-  if (e->cs_host) HIP_IGNORE(hipHostFree(e->cs_host));
-  for (int i = 0; i < 2; i++)
-    if (e->csa_buf[i]) HIP_IGNORE(hipHostFree(e->csa_buf[i]));
-  if (e->csa_ev) HIP_IGNORE(hipEventDestroy(e->csa_ev));
-  if (e->ce_s1) HIP_IGNORE(hipFree(e->ce_s1));
-  if (e->ce_s2) HIP_IGNORE(hipFree(e->ce_s2));
-  if (e->ce_meta) HIP_IGNORE(hipFree(e->ce_meta));
-  if (e->ce_cmd) HIP_IGNORE(hipFree(e->ce_cmd));
-  for (u8* p : {e->ck_s, e->ck_list, e->ck_log, e->ck_ref, e->ck_sec})
-    if (p) HIP_IGNORE(hipFree(p));
-  if (e->ck_host) HIP_IGNORE(hipHostFree(e->ck_host));
-  for (int i = 0; i < 3; i++)
-    if (e->ce_host[i]) HIP_IGNORE(hipHostFree(e->ce_host[i]));
-  if (e->wire_dev) HIP_IGNORE(hipFree(e->wire_dev));
-  if (e->wire_meta) HIP_IGNORE(hipFree(e->wire_meta));
-  if (e->wire_rec) HIP_IGNORE(hipFree(e->wire_rec));
-  if (e->wire_in) HIP_IGNORE(hipFree(e->wire_in));
-  if (e->wire_big_buf) HIP_IGNORE(hipFree(e->wire_big_buf));
-  if (e->stream) HIP_IGNORE(hipStreamDestroy(e->stream));
-  delete e;
+  delete e;  // ~rbe_engine, then every buffer's owner, the stream last
   return RBE_OK;
 }
 
@@ -1627,15 +1597,15 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
       if (pages > C.pool_pages) C.pool_pages = (u32)std::min<u64>(pages, cap);
     }
   }
-  rbe_engine* e = new (std::nothrow) rbe_engine();
+  // the guard owns the engine until the last step has succeeded: any return
+  // before that releases whatever has been allocated so far
+  std::unique_ptr<rbe_engine> guard(new (std::nothrow) rbe_engine());
+  rbe_engine* e = guard.get();
   if (!e) return RBE_E_NOMEM;
   e->cfg = *cfg;
   e->C = C;
   e->device = cfg->device;
-  if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
-    rbe_destroy(e);
-    return RBE_E_HIP;
-  }
+  if (hipStreamCreateWithFlags(&e->stream.s, hipStreamNonBlocking) != hipSuccess) return RBE_E_HIP;
   HIP_IGNORE(hipEventCreate(&e->ev0));
   HIP_IGNORE(hipEventCreate(&e->ev1));
   for (int i = 0; i < 2; i++) {
@@ -1645,19 +1615,8 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
   u64 parts[kPlaneAllocs];
   bytes_of(C, parts);
   void* ptrs[kPlaneAllocs];
-  for (int i = 0; i < kPlaneAllocs; i++) {
-    u64 b = parts[i] ? parts[i] : 16;
-    if (hipMalloc(&ptrs[i], b) != hipSuccess) {
-      for (int j = 0; j < i; j++) e->allocs.push_back(ptrs[j]);
-      rbe_destroy(e);
-      return RBE_E_NOMEM;
-    }
-    e->allocs.push_back(ptrs[i]);
-    if (hipMemsetAsync(ptrs[i], 0, b, e->stream) != hipSuccess) {
-      rbe_destroy(e);
-      return RBE_E_HIP;
-    }
-  }
+  for (int i = 0; i < kPlaneAllocs; i++)
+    if ((rc = dev_fixed(e, &ptrs[i], parts[i] ? parts[i] : 16, true))) return rc;
   Planes& P = e->P;
   P.hot = (Hot*)ptrs[0];
   P.core = (Core*)ptrs[1];
@@ -1700,14 +1659,13 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
     // in place, and the demotion's move list (at most every HBM page in a pass)
     const u64 hb = (u64)C.host_pages * kPageEnts * sizeof(Ent);
     e->cmove_cap = (u32)std::min<u64>(std::max<u64>(C.pool_pages, 64), 1u << 20);
+    const u64 mb = (u64)e->cmove_cap * sizeof(ColdMove);
     void* dp = nullptr;
-    if (hipHostMalloc((void**)&e->hpool_host, hb, hipHostMallocMapped) != hipSuccess ||
-        !e->hpool_host || hipHostGetDevicePointer(&dp, e->hpool_host, 0) != hipSuccess || !dp ||
-        hipMalloc((void**)&e->cmove, (u64)e->cmove_cap * sizeof(ColdMove)) != hipSuccess) {
-      rbe_destroy(e);
+    if (e->hpool_host.reserve_cap(hb, hb) ||
+        hipHostGetDevicePointer(&dp, e->hpool_host.p(), 0) != hipSuccess || !dp ||
+        e->cmove.reserve_cap(mb, mb))
       return RBE_E_NOMEM;
-    }
-    HIP_IGNORE(hipMemsetAsync(e->cmove, 0, (u64)e->cmove_cap * sizeof(ColdMove), e->stream));
+    HIP_IGNORE(hipMemsetAsync(e->cmove.p(), 0, mb, e->stream));
     // the tier's constants live in SpillCtl (rbe_types.h): the words from
     // `hpool` to `fa_n`, uploaded after the planes' zero fill on the same stream
     SpillCtl& t = e->tier_init;
@@ -1719,10 +1677,8 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
     t.fa_mask = (u32)(fa_ring_size(C.pool_pages) - 1);
     const size_t o0 = offsetof(SpillCtl, hpool), o1 = offsetof(SpillCtl, pad1);
     if (hipMemcpyAsync((u8*)P.sctl + o0, (const u8*)&t + o0, o1 - o0, hipMemcpyHostToDevice,
-                       e->stream) != hipSuccess) {
-      rbe_destroy(e);
+                       e->stream) != hipSuccess)
       return RBE_E_HIP;
-    }
   }
   // page 0 is the null page: the bump counter starts at 1
   HIP_IGNORE(hipMemsetD32Async((hipDeviceptr_t)&P.sctl->bump, 1, 1, e->stream));
@@ -1732,15 +1688,9 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
   e->hin.init(C.n_rep, C.n, C.in_cap, C.heap_bytes);
   e->hin.owner = C.rep_world > 1 ? &e->C : nullptr;
   if (C.heap_bytes) {
-    if (hipMalloc(&e->heap, C.heap_bytes) != hipSuccess ||
-        hipMalloc(&e->heap_dev, 2 * sizeof(u64)) != hipSuccess) {
-      if (e->heap) e->allocs.push_back(e->heap);
-      rbe_destroy(e);
-      return RBE_E_NOMEM;
-    }
-    e->allocs.push_back(e->heap);
-    e->allocs.push_back(e->heap_dev);
-    HIP_IGNORE(hipMemsetAsync(e->heap_dev, 0, 2 * sizeof(u64), e->stream));
+    if ((rc = dev_fixed(e, &e->heap, C.heap_bytes)) ||
+        (rc = dev_fixed(e, &e->heap_dev, 2 * sizeof(u64), true)))
+      return rc;
     P.heap_head = e->heap_dev;
     // the lowest live record, on demand (HostHeap::room)
     e->hin.heap.low_fn = [e](u64* lo) -> int {
@@ -1760,17 +1710,9 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
       return RBE_OK;
     };
   }
-  if (hipMalloc(&P.counters, kCtrWords * sizeof(u64)) != hipSuccess) {
-    rbe_destroy(e);
-    return RBE_E_NOMEM;
-  }
-  e->allocs.push_back(P.counters);
-  HIP_IGNORE(hipMemsetAsync(P.counters, 0, kCtrWords * sizeof(u64), e->stream));
-  if (hipMalloc(&e->d_clk, 2 * sizeof(u32)) != hipSuccess) {
-    rbe_destroy(e);
-    return RBE_E_NOMEM;
-  }
-  HIP_IGNORE(hipMemsetAsync(e->d_clk, 0, 2 * sizeof(u32), e->stream));
+  if ((rc = dev_fixed(e, &P.counters, kCtrWords * sizeof(u64), true)) ||
+      (rc = dev_fixed(e, &e->d_clk, 2 * sizeof(u32), true)))
+    return rc;
   if (const char* wb = getenv("RBE_WIRE_BIG")) e->wire_big = strtoull(wb, nullptr, 10);
   if (const char* cs = getenv("RBE_COLLECT_STAGE")) e->ce_stage = cs[0] != '0';
   if (const char* fg = getenv("RBE_FAST_GRID")) g_fast_grid = (unsigned)strtoul(fg, nullptr, 10);
@@ -1783,10 +1725,7 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
                      : strcmp(mode, "fused") == 0 ? 0
                      : strcmp(mode, "split") == 0 ? 1
                                                   : 3);
-  if (C.n_rep >= (1ull << 32)) {
-    rbe_destroy(e);
-    return RBE_E_INVALID;  // list entries are 32-bit replica indices
-  }
+  if (C.n_rep >= (1ull << 32)) return RBE_E_INVALID;  // list entries are 32-bit replica indices
   {
     // lists 0 and 1 come from k_triage alone: a shard's region holds the
     // replicas of its blocks; list 2 takes pushes from every pipeline kernel,
@@ -1799,15 +1738,10 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
     e->L.off[1] = kShards * per;
     e->L.off[2] = 2 * kShards * per;
   }
-  if (hipMalloc(&e->L.idx, (e->L.off[2] + kShards * C.n_rep) * sizeof(u32)) != hipSuccess ||
-      hipMalloc(&e->L.aux, e->L.off[2] * sizeof(u32)) != hipSuccess ||
-      hipMalloc(&e->L.counts, kListCounts * sizeof(u32)) != hipSuccess) {
-    rbe_destroy(e);
-    return RBE_E_NOMEM;
-  }
-  e->allocs.push_back(e->L.idx);
-  e->allocs.push_back(e->L.aux);
-  e->allocs.push_back(e->L.counts);
+  if ((rc = dev_fixed(e, &e->L.idx, (e->L.off[2] + kShards * C.n_rep) * sizeof(u32))) ||
+      (rc = dev_fixed(e, &e->L.aux, e->L.off[2] * sizeof(u32))) ||
+      (rc = dev_fixed(e, &e->L.counts, kListCounts * sizeof(u32), true)))
+    return rc;
   {
     // group sleep in list mode (k_triage): two awake lists of one region per
     // k_triage block, their counts, the sleeping totals and the scan-round
@@ -1817,15 +1751,9 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
     u32* w = nullptr;
     u8* al = nullptr;
     const u64 wbytes = 2 * (u64)nblk * sizeof(u32) + 6 * sizeof(u64) + 256;
-    if (hipMalloc(&al, 2 * (u64)nblk * gb * sizeof(u32)) != hipSuccess ||
-        hipMalloc(&w, wbytes) != hipSuccess) {
-      if (al) HIP_IGNORE(hipFree(al));
-      rbe_destroy(e);
-      return RBE_E_NOMEM;
-    }
-    e->allocs.push_back(al);
-    e->allocs.push_back(w);
-    HIP_IGNORE(hipMemsetAsync(w, 0, wbytes, e->stream));
+    if ((rc = dev_fixed(e, &al, 2 * (u64)nblk * gb * sizeof(u32))) ||
+        (rc = dev_fixed(e, &w, wbytes, true)))
+      return rc;
     e->L.al[0] = (u32*)al;
     e->L.al[1] = (u32*)al + (u64)nblk * gb;
     e->L.al_nblk = nblk;
@@ -1840,13 +1768,7 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
   e->L.vgrid = 700u;
   if (const char* vg = getenv("RBE_FAST_VGRID")) e->L.vgrid = (u32)strtoul(vg, nullptr, 10);
   // pack counters, then the sticky overflow flag of the fixed-layout exchange
-  if (hipMalloc(&e->xcount, (kXchgMaxWorld * XS_NUM + 1) * sizeof(u32)) != hipSuccess) {
-    rbe_destroy(e);
-    return RBE_E_NOMEM;
-  }
-  e->allocs.push_back(e->xcount);
-  HIP_IGNORE(hipMemsetAsync(e->xcount, 0, (kXchgMaxWorld * XS_NUM + 1) * sizeof(u32), e->stream));
-  HIP_IGNORE(hipMemsetAsync(e->L.counts, 0, kListCounts * sizeof(u32), e->stream));
+  if ((rc = dev_fixed(e, &e->xcount, (kXchgMaxWorld * XS_NUM + 1) * sizeof(u32), true))) return rc;
   rc = dispatch_n(C.n, [&](auto NN) {
     constexpr int N = decltype(NN)::value;
     hipLaunchKernelGGL(k_launch<N>, dim3(grid_for(C.n_rep)), dim3(kBlock), 0, e->stream, e->P,
@@ -1854,11 +1776,8 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
     HIP_OK(hipGetLastError());
     return RBE_OK;
   });
-  if (rc || hipStreamSynchronize(e->stream) != hipSuccess) {
-    rbe_destroy(e);
-    return rc ? rc : RBE_E_HIP;
-  }
-  *out = e;
+  if (rc || hipStreamSynchronize(e->stream) != hipSuccess) return rc ? rc : RBE_E_HIP;
+  *out = guard.release();
   return RBE_OK;
 }
 
@@ -1867,11 +1786,11 @@ static int launch_iso(rbe_engine* e) {
   const Params& C = e->C;
   if (!(C.iso_period && e->round > 0 && e->round % C.iso_period == 0)) return RBE_OK;
   if (C.rep_world > 1) {  // the leaders of groups whose replicas other ranks step
-    if (e->iso_round != e->round || !e->iso_dev) return RBE_E_STATE;
+    if (e->iso_round != e->round || !e->iso_dev.p()) return RBE_E_STATE;
     return dispatch_n(C.n, [&](auto NN) {
       constexpr int N = decltype(NN)::value;
       hipLaunchKernelGGL(k_iso_set<N>, dim3(grid_for(C.n_groups)), dim3(kBlock), 0, e->stream,
-                         e->P, e->C, e->round, (const u8*)e->iso_dev);
+                         e->P, e->C, e->round, (const u8*)e->iso_dev.p());
       HIP_OK(hipGetLastError());
       return RBE_OK;
     });
@@ -1907,22 +1826,11 @@ static int flush_inputs(rbe_engine* e) {
   const u64 o_sr = o_cr + nc * sizeof(CommitRec);
   const u64 total = o_sr + ns * sizeof(SnapRec);
   const u64 small = total - o_ar, pneed = small + nh + 64;
-  if (total + 64 > e->in_bytes) {
-    if (e->in_dev) HIP_OK(hipFree(e->in_dev));
-    e->in_dev = nullptr;
-    e->in_bytes = 0;
-    const u64 cap = (total + 64) * 2;
-    HIP_OK(hipMalloc((void**)&e->in_dev, cap));
-    e->in_bytes = cap;
-  }
-  if (pneed > e->in_pbytes[sl]) {
-    if (e->in_pinned[sl]) HIP_OK(hipHostFree(e->in_pinned[sl]));
-    e->in_pinned[sl] = nullptr;
-    e->in_pbytes[sl] = 0;
-    HIP_OK(hipHostMalloc((void**)&e->in_pinned[sl], pneed * 2, hipHostMallocDefault));
-    e->in_pbytes[sl] = pneed * 2;
-  }
-  u8* b = e->in_pinned[sl];
+  int rc;
+  if ((rc = e->in_dev.reserve_cap(total + 64, (total + 64) * 2)) ||
+      (rc = e->in_pinned[sl].reserve_cap(pneed, pneed * 2)))
+    return rc;
+  u8* b = e->in_pinned[sl].p();
   // payload heap bytes of the staged proposals: positions [flushed, head),
   // split where they cross the end of the ring
   if (nh) {
@@ -1940,9 +1848,9 @@ static int flush_inputs(rbe_engine* e) {
                           e->stream));
   }
   if (n) {
-    HIP_OK(hipMemcpyAsync(e->in_dev, h.reps.data(), n * sizeof(u64), hipMemcpyHostToDevice,
+    HIP_OK(hipMemcpyAsync(e->in_dev.p(), h.reps.data(), n * sizeof(u64), hipMemcpyHostToDevice,
                           e->stream));
-    HIP_OK(hipMemcpyAsync(e->in_dev + o_rec, h.recs.data(), n * sizeof(ExtIn),
+    HIP_OK(hipMemcpyAsync(e->in_dev.p() + o_rec, h.recs.data(), n * sizeof(ExtIn),
                           hipMemcpyHostToDevice, e->stream));
   }
   if (na) {
@@ -1951,7 +1859,7 @@ static int flush_inputs(rbe_engine* e) {
   }
   if (nc) memcpy(b + (o_cr - o_ar), h.commits.data(), nc * sizeof(CommitRec));
   if (ns) memcpy(b + (o_sr - o_ar), h.snaps.data(), ns * sizeof(SnapRec));
-  if (small) HIP_OK(hipMemcpyAsync(e->in_dev + o_ar, b, small, hipMemcpyHostToDevice, e->stream));
+  if (small) HIP_OK(hipMemcpyAsync(e->in_dev.p() + o_ar, b, small, hipMemcpyHostToDevice, e->stream));
   if (!h.ents.empty())
     HIP_OK(hipMemcpyAsync(e->P.in_ents, h.ents.data(), h.ents.size() * sizeof(Ent),
                           hipMemcpyHostToDevice, e->stream));
@@ -1966,10 +1874,10 @@ static int flush_inputs(rbe_engine* e) {
     const u64 m = ph == 0 ? m0 : (ph == 1 ? nc : ns);
     if (!m) continue;
     hipLaunchKernelGGL(k_ext_scatter, dim3(grid_for(m)), dim3(kBlock), 0, e->stream, e->P,
-                       e->C.n, (const u64*)e->in_dev, (const ExtIn*)(e->in_dev + o_rec), pn,
-                       (const u64*)(e->in_dev + o_ar), (const u64*)(e->in_dev + o_av), pa,
-                       (const CommitRec*)(e->in_dev + o_cr), pc,
-                       (const SnapRec*)(e->in_dev + o_sr), ps, e->C, e->L, e->round & 1u);
+                       e->C.n, (const u64*)e->in_dev.p(), (const ExtIn*)(e->in_dev.p() + o_rec), pn,
+                       (const u64*)(e->in_dev.p() + o_ar), (const u64*)(e->in_dev.p() + o_av), pa,
+                       (const CommitRec*)(e->in_dev.p() + o_cr), pc,
+                       (const SnapRec*)(e->in_dev.p() + o_sr), ps, e->C, e->L, e->round & 1u);
     HIP_OK(hipGetLastError());
   }
   HIP_OK(hipEventRecord(e->in_ev[sl], e->stream));
@@ -2216,9 +2124,9 @@ int rbe_launch(rbe_engine* e, uint64_t n, const uint64_t* replica, const rbe_lau
   const u64 b_b = bodies.size() * sizeof(Body);
   const u64 b_pg = np ? n * sizeof(LaunchPg) : 0, b_po = np ? (n + 1) * sizeof(u32) : 0;
   const u64 bytes = b_rec + b_t + b_b + b_pg + b_po + np * sizeof(u32) + 64;
-  rc = grow(&e->gat_dev, &e->gat_dev_bytes, bytes, false);  // (engine scratch, as rbe_replace_node)
+  rc = e->gat_dev.reserve(bytes);  // (engine scratch, as rbe_replace_node)
   if (rc) return rc;
-  u8* d = e->gat_dev;
+  u8* d = e->gat_dev.p();
   const LaunchRec* d_rec = (const LaunchRec*)d;
   const u64* d_t = (const u64*)(d + b_rec);
   const Body* d_b = (const Body*)(d + b_rec + b_t);
@@ -2287,13 +2195,13 @@ int rbe_apply_config_change(rbe_engine* e, uint64_t n, const uint64_t* replica,
     // one gather kernel in the engine's scratch buffer: replicas in, packed
     // memberships out, one copy each way
     const u64 ob = (n * sizeof(u64) + 15) & ~15ull;
-    const int rc = grow(&e->gat_dev, &e->gat_dev_bytes, ob + n * sizeof(u32), false);
+    const int rc = e->gat_dev.reserve(ob + n * sizeof(u32));
     if (rc) return rc;
-    HIP_OK(hipMemcpyAsync(e->gat_dev, replica, n * sizeof(u64), hipMemcpyHostToDevice, e->stream));
+    HIP_OK(hipMemcpyAsync(e->gat_dev.p(), replica, n * sizeof(u64), hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(k_ms_gather, dim3(grid_for(n)), dim3(kBlock), 0, e->stream, e->P,
-                       (const u64*)e->gat_dev, (u64)n, (u32*)(e->gat_dev + ob));
+                       (const u64*)e->gat_dev.p(), (u64)n, (u32*)(e->gat_dev.p() + ob));
     HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(ms.data(), e->gat_dev + ob, n * sizeof(u32), hipMemcpyDeviceToHost,
+    HIP_OK(hipMemcpyAsync(ms.data(), e->gat_dev.p() + ob, n * sizeof(u32), hipMemcpyDeviceToHost,
                           e->stream));
     HIP_OK(hipStreamSynchronize(e->stream));
   }
@@ -2326,12 +2234,7 @@ int rbe_set_node_ids(rbe_engine* e, uint64_t first_group, uint64_t count, const 
   if (rc || count == 0) return rc;
   HIP_OK(hipSetDevice(e->device));
   const u64 bytes = e->hin.ids.size() * sizeof(u64);
-  if (!e->P.node_ids) {
-    u64* d = nullptr;
-    if (hipMalloc(&d, bytes) != hipSuccess) return RBE_E_NOMEM;
-    e->allocs.push_back(d);
-    e->P.node_ids = d;
-  }
+  if ((rc = node_ids_alloc(e, bytes))) return rc;
   HIP_OK(hipMemcpyAsync((void*)e->P.node_ids, e->hin.ids.data(), bytes, hipMemcpyHostToDevice,
                         e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
@@ -2349,11 +2252,11 @@ int rbe_replace_node(rbe_engine* e, uint64_t n, const uint64_t* replica, const u
     return RBE_E_STATE;
   if (n == 0) return RBE_OK;
   HIP_OK(hipSetDevice(e->device));
-  // (the engine's scratch buffer: no allocation per call, nothing to free on
-  // an error path; every user synchronizes before it returns)
-  rc = grow(&e->gat_dev, &e->gat_dev_bytes, n * sizeof(u64) + n * sizeof(u32), false);
+  // (the engine's scratch buffer: no allocation per call; every user
+  // synchronizes before it returns, so the next one may regrow it)
+  rc = e->gat_dev.reserve(n * sizeof(u64) + n * sizeof(u32));
   if (rc) return rc;
-  u64* d = (u64*)e->gat_dev;
+  u64* d = (u64*)e->gat_dev.p();
   u32* dref = (u32*)(d + n);
   std::vector<u32> refd(n);
   HIP_OK(hipMemcpyAsync(d, replica, n * sizeof(u64), hipMemcpyHostToDevice, e->stream));
@@ -2374,10 +2277,7 @@ int rbe_replace_node(rbe_engine* e, uint64_t n, const uint64_t* replica, const u
   for (u64 i = 0; i < n; i++) e->hin.assign_node(e->C.n_groups, replica[i], node_id[i]);
   const u64 bytes = e->hin.ids.size() * sizeof(u64);
   if (!e->P.node_ids) {
-    u64* t = nullptr;
-    if (hipMalloc(&t, bytes) != hipSuccess) return RBE_E_NOMEM;
-    e->allocs.push_back(t);
-    e->P.node_ids = t;
+    if ((rc = node_ids_alloc(e, bytes))) return rc;
     drop_graphs(e);  // kernels take the planes by value
     HIP_OK(hipMemcpyAsync((void*)e->P.node_ids, e->hin.ids.data(), bytes, hipMemcpyHostToDevice,
                           e->stream));
@@ -2425,7 +2325,7 @@ extern "C" int rbe_debug_full_prof(rbe_engine* e, uint64_t* out, uint64_t cap, u
   if (!e || !n) return RBE_E_INVALID;
   HIP_OK(hipSetDevice(e->device));
   if (!e->P.prof) {
-    HIP_OK(hipMalloc((void**)&e->P.prof, (kProfHdr + 4 * kFullProfCap) * sizeof(u64)));
+    if (dev_fixed(e, &e->P.prof, (kProfHdr + 4 * kFullProfCap) * sizeof(u64))) return RBE_E_HIP;
     HIP_OK(hipMemset(e->P.prof, 0, kProfHdr * sizeof(u64)));  // counter | phase sums (rbe_debug_phases)
     drop_graphs(e);
     *n = 0;
@@ -2658,17 +2558,16 @@ int rbe_push_messages(rbe_engine* e, uint64_t n, const uint64_t* group, const rb
   });
   if (rc) return rc;
   const size_t bytes = c.size() * sizeof(XCnt) + m.size() * sizeof(XMsg) + x.size() * sizeof(XEnt);
-  u8* d = nullptr;
-  if (bytes) HIP_OK(hipMalloc(&d, bytes));
+  Scratch<DevMem> tmp;  // freed on every return below
+  if ((rc = tmp.reserve_cap(bytes, bytes))) return rc;
+  u8* d = tmp.p();
   const size_t om = c.size() * sizeof(XCnt), ox = om + m.size() * sizeof(XMsg);
   if (!c.empty()) HIP_OK(hipMemcpyAsync(d, c.data(), om, hipMemcpyHostToDevice, e->stream));
   if (!m.empty())
     HIP_OK(hipMemcpyAsync(d + om, m.data(), ox - om, hipMemcpyHostToDevice, e->stream));
   if (!x.empty())
     HIP_OK(hipMemcpyAsync(d + ox, x.data(), bytes - ox, hipMemcpyHostToDevice, e->stream));
-  rc = xchg_scatter(e, d, c.size(), d + om, m.size(), d + ox, x.size());
-  if (d) HIP_IGNORE(hipFree(d));
-  return rc;
+  return xchg_scatter(e, d, c.size(), d + om, m.size(), d + ox, x.size());
 }
 
 int rbe_kernel_name(const rbe_engine* e, int32_t kernel, char* buf, uint32_t cap) {
@@ -2925,19 +2824,6 @@ int rbe_get_messages(rbe_engine* e, uint64_t replica, rbe_message* out, uint32_t
   return RBE_OK;
 }
 
-// grow a device (pinned = false) or pinned host buffer to at least `need` bytes
-static int grow(u8** p, u64* have, u64 need, bool pinned) {
-  if (need <= *have) return RBE_OK;
-  if (*p) HIP_OK(pinned ? hipHostFree(*p) : hipFree(*p));
-  *p = nullptr;
-  *have = 0;
-  const u64 cap = need + need / 2 + 4096;
-  if (pinned) HIP_OK(hipHostMalloc((void**)p, cap, hipHostMallocDefault));
-  else HIP_OK(hipMalloc((void**)p, cap));
-  *have = cap;
-  return RBE_OK;
-}
-
 int rbe_collect_outputs(rbe_engine* e, uint64_t first, uint64_t count, rbe_outputs* out) {
   if (!e || !out || count == 0 || first >= e->C.n_rep || count > e->C.n_rep - first)
     return RBE_E_INVALID;
@@ -2953,10 +2839,10 @@ int rbe_collect_outputs(rbe_engine* e, uint64_t first, uint64_t count, rbe_outpu
   const u64 o_pre = al(2ull * nb * sizeof(u32)), o_moff = o_pre + al(scan_words(2, nb) * sizeof(u64));
   const u64 o_roff = o_moff + al((count + 1) * sizeof(u64));
   const u64 o_rec = o_roff + al((count + 1) * sizeof(u64));
-  int rc = grow(&e->out_dev, &e->out_dev_bytes, o_rec, false);
+  int rc = e->out_dev.reserve(o_rec);
   if (rc) return rc;
-  u32* bsum = (u32*)e->out_dev;
-  u64* pre = (u64*)(e->out_dev + o_pre);
+  u32* bsum = (u32*)e->out_dev.p();
+  u64* pre = (u64*)(e->out_dev.p() + o_pre);
   hipLaunchKernelGGL(k_out_count, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C, (u64)first,
                      (u64)count, e->round, bsum);
   if ((rc = launch_scan<2>(e->stream, bsum, nb, pre))) return rc;
@@ -2965,24 +2851,19 @@ int rbe_collect_outputs(rbe_engine* e, uint64_t first, uint64_t count, rbe_outpu
   HIP_OK(hipStreamSynchronize(e->stream));
   const u64 o_rtr = o_rec + al(tot[0] * sizeof(rbe_message));
   const u64 need = o_rtr + al(tot[1] * sizeof(rbe_ready_to_read));
-  if (need > e->out_dev_bytes) {  // keep the block prefixes across the regrow
-    std::vector<u64> keep(2ull * nb + 2);
-    HIP_OK(hipMemcpy(keep.data(), pre, keep.size() * sizeof(u64), hipMemcpyDeviceToHost));
-    if ((rc = grow(&e->out_dev, &e->out_dev_bytes, need, false))) return rc;
-    pre = (u64*)(e->out_dev + o_pre);
-    HIP_OK(hipMemcpy(pre, keep.data(), keep.size() * sizeof(u64), hipMemcpyHostToDevice));
-  }
-  u8* d = e->out_dev;
+  // (the block prefixes survive a regrow)
+  if ((rc = e->out_dev.reserve_keep(need, o_moff, e->stream))) return rc;
+  u8* d = e->out_dev.p();
   hipLaunchKernelGGL(k_out_write, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C, (u64)first,
                      (u64)count, e->round, (const u64*)(d + o_pre), (u64*)(d + o_moff),
                      (rbe_message*)(d + o_rec), (u64*)(d + o_roff),
                      (rbe_ready_to_read*)(d + o_rtr));
   HIP_OK(hipGetLastError());
   // one copy of offsets and records into the pinned host buffer
-  if ((rc = grow(&e->out_host, &e->out_host_bytes, need - o_moff, true))) return rc;
-  HIP_OK(hipMemcpyAsync(e->out_host, d + o_moff, need - o_moff, hipMemcpyDeviceToHost, e->stream));
+  if ((rc = e->out_host.reserve(need - o_moff))) return rc;
+  HIP_OK(hipMemcpyAsync(e->out_host.p(), d + o_moff, need - o_moff, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
-  u8* h = e->out_host;
+  u8* h = e->out_host.p();
   out->n_messages = tot[0];
   out->n_ready_to_reads = tot[1];
   out->msg_off = (const uint64_t*)(h + (o_moff - o_moff));
@@ -3008,12 +2889,12 @@ int rbe_collect_step(rbe_engine* e, uint64_t first, uint64_t count, uint32_t fla
   // records, laid out as the host copy: replicas | updates | msg offsets |
   // rtr offsets | messages | ReadyToReads
   const u64 o_pre = al(3ull * nb * sizeof(u32)), o_rep = o_pre + al(scan_words(3, nb) * sizeof(u64));
-  int rc = grow(&e->cs_dev, &e->cs_dev_bytes, o_rep, false);
+  int rc = e->cs_dev.reserve(o_rep);
   if (rc) return rc;
-  u64* pre = (u64*)(e->cs_dev + o_pre);
+  u64* pre = (u64*)(e->cs_dev.p() + o_pre);
   hipLaunchKernelGGL(k_cs_count, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C, (u64)first,
-                     (u64)count, e->round, flags, (u32*)e->cs_dev);
-  if ((rc = launch_scan<3>(e->stream, (const u32*)e->cs_dev, nb, pre))) return rc;
+                     (u64)count, e->round, flags, (u32*)e->cs_dev.p());
+  if ((rc = launch_scan<3>(e->stream, (const u32*)e->cs_dev.p(), nb, pre))) return rc;
   u64 tot[3];
   HIP_OK(hipMemcpyAsync(tot, pre + 3ull * nb, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
@@ -3024,24 +2905,19 @@ int rbe_collect_step(rbe_engine* e, uint64_t first, uint64_t count, uint32_t fla
   const u64 o_msg = o_roff + al((n + 1) * sizeof(u64));
   const u64 o_rtr = o_msg + al(tot[1] * sizeof(rbe_message));
   const u64 need = o_rtr + al(tot[2] * sizeof(rbe_ready_to_read));
-  if (need > e->cs_dev_bytes) {  // keep the block prefixes across the regrow
-    std::vector<u64> keep(3ull * nb + 3);
-    HIP_OK(hipMemcpy(keep.data(), pre, keep.size() * sizeof(u64), hipMemcpyDeviceToHost));
-    if ((rc = grow(&e->cs_dev, &e->cs_dev_bytes, need, false))) return rc;
-    pre = (u64*)(e->cs_dev + o_pre);
-    HIP_OK(hipMemcpy(pre, keep.data(), keep.size() * sizeof(u64), hipMemcpyHostToDevice));
-  }
-  u8* d = e->cs_dev;
+  // (the block prefixes survive a regrow)
+  if ((rc = e->cs_dev.reserve_keep(need, o_rep, e->stream))) return rc;
+  u8* d = e->cs_dev.p();
   hipLaunchKernelGGL(k_cs_write, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C, (u64)first,
                      (u64)count, e->round, flags, (const u64*)(d + o_pre), (u64*)(d + o_rep),
                      (rbe_update*)(d + o_upd), (u64*)(d + o_moff), (rbe_message*)(d + o_msg),
                      (u64*)(d + o_roff), (rbe_ready_to_read*)(d + o_rtr),
                      CsCaps{n, tot[1], tot[2], nullptr});
   HIP_OK(hipGetLastError());
-  if ((rc = grow(&e->cs_host, &e->cs_host_bytes, need - o_rep, true))) return rc;
-  HIP_OK(hipMemcpyAsync(e->cs_host, d + o_rep, need - o_rep, hipMemcpyDeviceToHost, e->stream));
+  if ((rc = e->cs_host.reserve(need - o_rep))) return rc;
+  HIP_OK(hipMemcpyAsync(e->cs_host.p(), d + o_rep, need - o_rep, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
-  u8* h = e->cs_host - o_rep;
+  u8* h = e->cs_host.p() - o_rep;
   out->n = n;
   out->n_messages = tot[1];
   out->n_ready_to_reads = tot[2];
@@ -3083,26 +2959,20 @@ int rbe_collect_step_begin(rbe_engine* e, uint64_t first, uint64_t count, uint32
   const u64 need = csa_layout(e->csa_cap, o);
   const u32 sl = e->csa_slot;
   e->csa_slot ^= 1u;
-  if (need > e->csa_bytes[sl]) {
-    if (e->csa_buf[sl]) HIP_OK(hipHostFree(e->csa_buf[sl]));
-    e->csa_buf[sl] = nullptr;
-    e->csa_bytes[sl] = 0;
-    HIP_OK(hipHostMalloc((void**)&e->csa_buf[sl], need, hipHostMallocMapped));
-    e->csa_bytes[sl] = need;
-  }
-  e->csa_host = e->csa_buf[sl];
+  int rc = e->csa_buf[sl].reserve_cap(need, need);
+  if (rc) return rc;
+  e->csa_host = e->csa_buf[sl].p();
   if (!e->csa_ev) HIP_OK(hipEventCreateWithFlags(&e->csa_ev, hipEventDisableTiming));
   u8* d = nullptr;
   HIP_OK(hipHostGetDevicePointer((void**)&d, e->csa_host, 0));
   const u32 nb = grid_for(count);
   auto al = [](u64 x) { return (x + 255) & ~255ull; };
   const u64 o_pre = al(3ull * nb * sizeof(u32)), o_end = o_pre + al(scan_words(3, nb) * sizeof(u64));
-  int rc = grow(&e->cs_dev, &e->cs_dev_bytes, o_end, false);
-  if (rc) return rc;
-  const u64* pre = (const u64*)(e->cs_dev + o_pre);
+  if ((rc = e->cs_dev.reserve(o_end))) return rc;
+  const u64* pre = (const u64*)(e->cs_dev.p() + o_pre);
   hipLaunchKernelGGL(k_cs_count, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C, (u64)first,
-                     (u64)count, e->round, flags, (u32*)e->cs_dev);
-  if ((rc = launch_scan<3>(e->stream, (const u32*)e->cs_dev, nb, (u64*)pre))) return rc;
+                     (u64)count, e->round, flags, (u32*)e->cs_dev.p());
+  if ((rc = launch_scan<3>(e->stream, (const u32*)e->cs_dev.p(), nb, (u64*)pre))) return rc;
   hipLaunchKernelGGL(k_cs_write, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C, (u64)first,
                      (u64)count, e->round, flags, pre, (u64*)(d + o[0]), (rbe_update*)(d + o[1]),
                      (u64*)(d + o[2]), (rbe_message*)(d + o[4]), (u64*)(d + o[3]),
@@ -3163,35 +3033,30 @@ int rbe_collect_updates(rbe_engine* e, uint64_t first, uint64_t count, rbe_updat
   auto al = [](u64 x) { return (x + 255) & ~255ull; };
   // device scratch: block sums (pairs) | block prefixes (+ totals) | replicas | records
   const u64 o_pre = al(2ull * nb * sizeof(u32)), o_rep = o_pre + al(scan_words(2, nb) * sizeof(u64));
-  int rc = grow(&e->upd_dev, &e->upd_dev_bytes, o_rep, false);
+  int rc = e->upd_dev.reserve(o_rep);
   if (rc) return rc;
-  u64* pre = (u64*)(e->upd_dev + o_pre);
+  u64* pre = (u64*)(e->upd_dev.p() + o_pre);
   hipLaunchKernelGGL(k_upd_count, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C.n, (u64)first,
-                     (u64)count, e->round, (u32*)e->upd_dev);
-  if ((rc = launch_scan<2>(e->stream, (const u32*)e->upd_dev, nb, pre))) return rc;
+                     (u64)count, e->round, (u32*)e->upd_dev.p());
+  if ((rc = launch_scan<2>(e->stream, (const u32*)e->upd_dev.p(), nb, pre))) return rc;
   u64 tot[2];
   HIP_OK(hipMemcpyAsync(tot, pre + 2ull * nb, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
   const u64 o_rec = o_rep + al(tot[0] * sizeof(u64)), need = o_rec + al(tot[0] * sizeof(rbe_update));
-  if (need > e->upd_dev_bytes) {  // keep the block prefixes across the regrow
-    std::vector<u64> keep(2ull * nb + 2);
-    HIP_OK(hipMemcpy(keep.data(), pre, keep.size() * sizeof(u64), hipMemcpyDeviceToHost));
-    if ((rc = grow(&e->upd_dev, &e->upd_dev_bytes, need, false))) return rc;
-    pre = (u64*)(e->upd_dev + o_pre);
-    HIP_OK(hipMemcpy(pre, keep.data(), keep.size() * sizeof(u64), hipMemcpyHostToDevice));
-  }
-  u8* d = e->upd_dev;
+  // (the block prefixes survive a regrow)
+  if ((rc = e->upd_dev.reserve_keep(need, o_rep, e->stream))) return rc;
+  u8* d = e->upd_dev.p();
   hipLaunchKernelGGL(k_upd_write, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C.n, (u64)first,
                      (u64)count, e->round, (const u64*)(d + o_pre), (u64*)(d + o_rep),
                      (rbe_update*)(d + o_rec));
   HIP_OK(hipGetLastError());
-  if ((rc = grow(&e->upd_host, &e->upd_host_bytes, need - o_rep, true))) return rc;
+  if ((rc = e->upd_host.reserve(need - o_rep))) return rc;
   if (need > o_rep)
-    HIP_OK(hipMemcpyAsync(e->upd_host, d + o_rep, need - o_rep, hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipMemcpyAsync(e->upd_host.p(), d + o_rep, need - o_rep, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
   out->n = tot[0];
-  out->replica = (const uint64_t*)e->upd_host;
-  out->updates = (const rbe_update*)(e->upd_host + (o_rec - o_rep));
+  out->replica = (const uint64_t*)e->upd_host.p();
+  out->updates = (const rbe_update*)(e->upd_host.p() + (o_rec - o_rep));
   return RBE_OK;
 }
 
@@ -3236,15 +3101,15 @@ static int read_window(rbe_engine* e, u64 replica, u64 lo, u64 hi, std::vector<u
   // the ring window and the cold log below it (the LogDB's entries above its
   // marker): one gather kernel, one copy
   const u64 n = hi - lo + 1;
-  int rc = grow(&e->gat_dev, &e->gat_dev_bytes, n * sizeof(Ent) + 256, false);
+  int rc = e->gat_dev.reserve(n * sizeof(Ent) + 256);
   if (rc) return rc;
-  u32* miss = (u32*)(e->gat_dev + n * sizeof(Ent));
+  u32* miss = (u32*)(e->gat_dev.p() + n * sizeof(Ent));
   HIP_OK(hipMemsetAsync(miss, 0, sizeof(u32), e->stream));
   hipLaunchKernelGGL(k_log_gather, dim3(1), dim3(kBlock), 0, e->stream, e->P, e->C, replica, lo, hi,
-                     (Ent*)e->gat_dev, miss);
+                     (Ent*)e->gat_dev.p(), miss);
   std::vector<Ent> en(n);
   u32 nmiss = 0;
-  HIP_OK(hipMemcpyAsync(en.data(), e->gat_dev, n * sizeof(Ent), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipMemcpyAsync(en.data(), e->gat_dev.p(), n * sizeof(Ent), hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipMemcpyAsync(&nmiss, miss, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
   if (nmiss) return RBE_E_STATE;  // compacted (ErrCompacted), or never handed over
@@ -3337,11 +3202,11 @@ static int ce_collect(rbe_engine* e, CeSrc s, const u64* h_rep, const u64* h_lo,
   // scratch 1: error word | block sums (pairs) | block prefixes (+ totals) | triples
   const u64 o_bs = 256, o_pre = o_bs + al(2ull * nb * sizeof(u32));
   const u64 o_tri = o_pre + al(scan_words(2, nb) * sizeof(u64)), tri = al(count * sizeof(u64));
-  int rc = grow(&e->ce_s1, &e->ce_s1_bytes, o_tri + (h_rep ? 3 * tri : 0), false);
+  int rc = e->ce_s1.reserve(o_tri + (h_rep ? 3 * tri : 0));
   if (rc) return rc;
-  u32* err = (u32*)e->ce_s1;
-  u32* bsum = (u32*)(e->ce_s1 + o_bs);
-  u64* pre = (u64*)(e->ce_s1 + o_pre);
+  u32* err = (u32*)e->ce_s1.p();
+  u32* bsum = (u32*)(e->ce_s1.p() + o_bs);
+  u64* pre = (u64*)(e->ce_s1.p() + o_pre);
   HIP_OK(hipMemsetAsync(err, 0, sizeof(u32), e->stream));
   // Heap records still staged for the next step (an rbe_launch's, whose
   // entries k_relaunch has already put into the logs; proposals not yet
@@ -3360,7 +3225,7 @@ static int ce_collect(rbe_engine* e, CeSrc s, const u64* h_rep, const u64* h_lo,
     HIP_OK(hipStreamSynchronize(e->stream));
   }
   if (h_rep) {
-    u64* d = (u64*)(e->ce_s1 + o_tri);
+    u64* d = (u64*)(e->ce_s1.p() + o_tri);
     HIP_OK(hipMemcpyAsync(d, h_rep, count * sizeof(u64), hipMemcpyHostToDevice, e->stream));
     HIP_OK(hipMemcpyAsync(d + tri / 8, h_lo, count * sizeof(u64), hipMemcpyHostToDevice, e->stream));
     HIP_OK(hipMemcpyAsync(d + 2 * (tri / 8), h_hi, count * sizeof(u64), hipMemcpyHostToDevice,
@@ -3384,19 +3249,19 @@ static int ce_collect(rbe_engine* e, CeSrc s, const u64* h_rep, const u64* h_lo,
   const u64 m_eoff = al(n * sizeof(u64)), m_ent = m_eoff + al((n + 1) * sizeof(u64));
   const u64 m_coff = m_ent + al((u64)nb2 * kBlock * sizeof(rbe_entry));
   const u64 m_end = m_coff + (cmds ? al((ne + 1) * sizeof(u64)) : 0);
-  if ((rc = grow(&e->ce_meta, &e->ce_meta_bytes, m_end, false))) return rc;
+  if ((rc = e->ce_meta.reserve(m_end))) return rc;
   // scratch 2: each range's first index | padded Cmd lengths | Cmd sources |
   // block sums | block prefixes (+ the Cmd total)
   const u64 o_len = al(n * sizeof(u64)), o_src = o_len + al(ne * sizeof(u32));
   const u64 o_bs2 = o_src + al(ne * sizeof(u64)), o_pre2 = o_bs2 + al(2ull * nb2 * sizeof(u32));
-  if ((rc = grow(&e->ce_s2, &e->ce_s2_bytes, o_pre2 + al(scan_words(2, nb2) * sizeof(u64)), false)))
+  if ((rc = e->ce_s2.reserve(o_pre2 + al(scan_words(2, nb2) * sizeof(u64)))))
     return rc;
-  u8* m = e->ce_meta;
-  u64* lo_at = (u64*)e->ce_s2;
-  u32* plen = (u32*)(e->ce_s2 + o_len);
-  u64* src = (u64*)(e->ce_s2 + o_src);
-  u32* bsum2 = (u32*)(e->ce_s2 + o_bs2);
-  u64* pre2 = (u64*)(e->ce_s2 + o_pre2);
+  u8* m = e->ce_meta.p();
+  u64* lo_at = (u64*)e->ce_s2.p();
+  u32* plen = (u32*)(e->ce_s2.p() + o_len);
+  u64* src = (u64*)(e->ce_s2.p() + o_src);
+  u32* bsum2 = (u32*)(e->ce_s2.p() + o_bs2);
+  u64* pre2 = (u64*)(e->ce_s2.p() + o_pre2);
   CeCaps caps{n, ne, 0};
   hipLaunchKernelGGL(k_ce_ranges, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C, s,
                      (const u64*)pre, (u64*)m, (u64*)(m + m_eoff), lo_at, caps, err);
@@ -3420,21 +3285,21 @@ static int ce_collect(rbe_engine* e, CeSrc s, const u64* h_rep, const u64* h_lo,
     HIP_OK(hipStreamSynchronize(e->stream));
     if (herr) return collect_rc(herr);
     cmd_bytes = units * 16;
-    if ((rc = grow(&e->ce_cmd, &e->ce_cmd_bytes, cmd_bytes, false))) return rc;
+    if ((rc = e->ce_cmd.reserve(cmd_bytes))) return rc;
     caps.cmd = cmd_bytes;
     if (cmd_bytes)
       hipLaunchKernelGGL(k_ce_cmds, dim3(std::min(nb2, kCeCmdGrid)),  // (4 waves a block)
                          dim3(kBlock), 0, e->stream, (const u8*)e->heap, ne,
                          (const rbe_entry*)(m + m_ent), (const u64*)src,
-                         (const u64*)(m + m_coff), e->ce_cmd, caps);
+                         (const u64*)(m + m_coff), e->ce_cmd.p(), caps);
   }
   HIP_OK(hipGetLastError());
-  if ((rc = grow(&e->ce_host[slot], &e->ce_host_bytes[slot], m_end + al(cmd_bytes), true)))
+  if ((rc = e->ce_host[slot].reserve(m_end + al(cmd_bytes))))
     return rc;
-  u8* h = e->ce_host[slot];
+  u8* h = e->ce_host[slot].p();
   HIP_OK(hipMemcpyAsync(h, m, m_end, hipMemcpyDeviceToHost, e->stream));
   if (cmd_bytes)
-    HIP_OK(hipMemcpyAsync(h + m_end, e->ce_cmd, cmd_bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipMemcpyAsync(h + m_end, e->ce_cmd.p(), cmd_bytes, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
   if (herr) return collect_rc(herr);
@@ -3576,9 +3441,9 @@ int rbe_wire_encode(rbe_engine* e, const rbe_wire_config* wc, uint64_t totals[4]
   const u64 o_msgs = al(ncell * 4), o_off = o_msgs + al(ncell * 4), o_pay = o_off + al(ncell * 4);
   const u64 o_bm = o_pay + al(nbatch * 8), o_bi = o_bm + al(nbatch * 4), o_fo = o_bi + al(nbatch * 4);
   const u64 o_fr = o_fo + al(nbatch * 8), o_tot = o_fr + al(nbatch * sizeof(WireFrame));
-  int rc = grow(&e->wire_meta, &e->wire_meta_bytes, o_tot + 64, false);
+  int rc = e->wire_meta.reserve(o_tot + 64);
   if (rc) return rc;
-  u8* m = e->wire_meta;
+  u8* m = e->wire_meta.p();
   HIP_OK(hipMemsetAsync(m + o_tot, 0, 64, e->stream));
   WireBufs B{(u32*)m, (u32*)(m + o_msgs), (u32*)(m + o_off), (u64*)(m + o_pay), (u32*)(m + o_bm),
              (u32*)(m + o_bi), (u64*)(m + o_fo), (WireFrame*)(m + o_fr), (u64*)(m + o_tot)};
@@ -3595,8 +3460,8 @@ int rbe_wire_encode(rbe_engine* e, const rbe_wire_config* wc, uint64_t totals[4]
   if (nseg <= 1) {
     hipLaunchKernelGGL(k_wire_batch, dim3((unsigned)nbatch), dim3(256), 0, e->stream, C, A, B);
   } else {
-    if ((rc = grow(&e->wire_big_buf, &e->wire_big_bytes, nbatch * nseg * 16, false))) return rc;
-    u64* seg_tot = (u64*)e->wire_big_buf;
+    if ((rc = e->wire_big_buf.reserve(nbatch * nseg * 16))) return rc;
+    u64* seg_tot = (u64*)e->wire_big_buf.p();
     hipLaunchKernelGGL(k_wire_batch_part, dim3((unsigned)nbatch, nseg), dim3(256), 0, e->stream,
                        C, A, B, seg_tot);
     hipLaunchKernelGGL(k_wire_batch_fix, dim3((unsigned)nbatch), dim3(256), 0, e->stream, C, A,
@@ -3611,18 +3476,18 @@ int rbe_wire_encode(rbe_engine* e, const rbe_wire_config* wc, uint64_t totals[4]
   HIP_OK(hipStreamSynchronize(e->stream));
   memset(e->wire_totals, 0, sizeof(e->wire_totals));
   if (tot[4]) return RBE_E_STATE;  // an entry's heap record was overwritten: no frames
-  rc = grow(&e->wire_dev, &e->wire_dev_bytes, tot[0] + 64, false);
+  rc = e->wire_dev.reserve(tot[0] + 64);
   if (rc) return rc;
   if (tot[1]) {
     rc = dispatch_n(C.n, [&](auto NN) {
       constexpr int N = decltype(NN)::value;
       hipLaunchKernelGGL((k_wire_write<N>), dim3(gc), dim3(256), 0, e->stream, e->P, C, A, B,
-                         (const u8*)e->heap, e->wire_dev);
+                         (const u8*)e->heap, e->wire_dev.p());
       return RBE_OK;
     });
     if (rc) return rc;
     hipLaunchKernelGGL(k_wire_trailers, dim3((unsigned)((nbatch + 255) / 256)), dim3(256), 0,
-                       e->stream, C, A, B, (u32)nbatch, e->wire_dev);
+                       e->stream, C, A, B, (u32)nbatch, e->wire_dev.p());
     // frames over 256 KiB of payload (wire_big, as the decode's chunked walk)
     // take their crc by 64 KiB segments over many blocks: their sizes come
     // from the frame index (read only when the stream could hold one)
@@ -3640,12 +3505,12 @@ int rbe_wire_encode(rbe_engine* e, const rbe_wire_config* wc, uint64_t totals[4]
       }
     }
     hipLaunchKernelGGL(k_wire_crc, dim3((unsigned)tot[1]), dim3(256), 0, e->stream, B,
-                       e->wire_dev, big);
+                       e->wire_dev.p(), big);
     if (!bigf.empty()) {
       const u64 nb = bigf.size(), ns = segs.size();
       const u64 o_acc = al(ns * sizeof(WireEncSeg)), o_bf = o_acc + al(tot[1] * 4);
-      if ((rc = grow(&e->wire_big_buf, &e->wire_big_bytes, o_bf + al(nb * 4), false))) return rc;
-      u8* b = e->wire_big_buf;
+      if ((rc = e->wire_big_buf.reserve(o_bf + al(nb * 4)))) return rc;
+      u8* b = e->wire_big_buf.p();
       WireEncSeg* dseg = (WireEncSeg*)b;
       u32 *acc = (u32*)(b + o_acc), *dbf = (u32*)(b + o_bf);
       HIP_OK(hipMemcpyAsync(dseg, segs.data(), ns * sizeof(WireEncSeg), hipMemcpyHostToDevice,
@@ -3653,9 +3518,9 @@ int rbe_wire_encode(rbe_engine* e, const rbe_wire_config* wc, uint64_t totals[4]
       HIP_OK(hipMemcpyAsync(dbf, bigf.data(), nb * 4, hipMemcpyHostToDevice, e->stream));
       HIP_OK(hipMemsetAsync(acc, 0, tot[1] * 4, e->stream));
       hipLaunchKernelGGL(k_wire_crc_seg, dim3((unsigned)ns), dim3(256), 0, e->stream, B,
-                         (const WireEncSeg*)dseg, acc, (const u8*)e->wire_dev);
+                         (const WireEncSeg*)dseg, acc, (const u8*)e->wire_dev.p());
       hipLaunchKernelGGL(k_wire_crc_fin, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0,
-                         e->stream, B, (const u32*)dbf, (u32)nb, (const u32*)acc, e->wire_dev);
+                         e->stream, B, (const u32*)dbf, (u32)nb, (const u32*)acc, e->wire_dev.p());
     }
     HIP_OK(hipGetLastError());
   }
@@ -3667,21 +3532,21 @@ int rbe_wire_encode(rbe_engine* e, const rbe_wire_config* wc, uint64_t totals[4]
 int rbe_wire_fetch(rbe_engine* e, void* out, uint64_t cap, rbe_wire_frame* frames,
                    uint32_t frames_cap) {
   if (!e) return RBE_E_INVALID;
-  if (!e->wire_meta) return RBE_E_STATE;
+  if (!e->wire_meta.p()) return RBE_E_STATE;
   HIP_OK(hipSetDevice(e->device));
   const u64 bytes = e->wire_totals[0], nf = e->wire_totals[1];
   if ((out && cap < bytes) || (frames && frames_cap < nf)) return RBE_E_NOMEM;
   static_assert(sizeof(WireFrame) == sizeof(rbe_wire_frame), "frame index layout");
   if (out && bytes)
-    HIP_OK(hipMemcpyAsync(out, e->wire_dev, bytes, hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipMemcpyAsync(out, e->wire_dev.p(), bytes, hipMemcpyDeviceToHost, e->stream));
   if (frames && nf)
-    HIP_OK(hipMemcpyAsync(frames, e->wire_meta + e->wire_frames_off, nf * sizeof(WireFrame),
+    HIP_OK(hipMemcpyAsync(frames, e->wire_meta.p() + e->wire_frames_off, nf * sizeof(WireFrame),
                           hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
   return RBE_OK;
 }
 
-// Decoded records of a byte stream, left in device memory (e->wire_rec):
+// Decoded records of a byte stream, left in device memory (e->wire_rec.p()):
 // messages in frame order, their entries (message j's from ent0[j]) and Cmd
 // bytes (message j's from cmd0[j]).
 struct WireDecoded {
@@ -3735,10 +3600,10 @@ static int wire_front(rbe_engine* e, const void* data, uint64_t bytes, WireFront
     slots += w.pos_cap;
   }
   const u64 o_fr = al(bytes), o_sp = o_fr + al(nf * sizeof(WireIn));
-  int rc = grow(&e->wire_in, &e->wire_in_bytes, o_sp + al(slots * sizeof(WireMsgPos)), false);
+  int rc = e->wire_in.reserve(o_sp + al(slots * sizeof(WireMsgPos)));
   if (rc) return rc;
-  WireIn* dfr = (WireIn*)(e->wire_in + o_fr);
-  WireMsgPos* spos = (WireMsgPos*)(e->wire_in + o_sp);
+  WireIn* dfr = (WireIn*)(e->wire_in.p() + o_fr);
+  WireMsgPos* spos = (WireMsgPos*)(e->wire_in.p() + o_sp);
   // big frames: their chunks and crc segments, in frame order (host lists,
   // uploaded with the frames)
   const u64 big = std::min<u64>(e->wire_big, 0xFFFFFF00ull);  // positions are u32
@@ -3762,8 +3627,8 @@ static int wire_front(rbe_engine* e, const void* data, uint64_t bytes, WireFront
     const u64 o_ch = o_base + al(nch * 4), o_bf = o_ch + al(nch * sizeof(WireChunk));
     const u64 o_c0 = o_bf + al(nbig * 4), o_sg = o_c0 + al(nbig * 4);
     const u64 need = o_sg + al(nseg * sizeof(WireSeg));
-    if ((rc = grow(&e->wire_big_buf, &e->wire_big_bytes, need, false))) return rc;
-    u8* b = e->wire_big_buf;
+    if ((rc = e->wire_big_buf.reserve(need))) return rc;
+    u8* b = e->wire_big_buf.p();
     exitv = (u32*)b;
     cntv = (u16*)(b + o_c);
     ent = (u32*)(b + o_ent);
@@ -3784,23 +3649,23 @@ static int wire_front(rbe_engine* e, const void* data, uint64_t bytes, WireFront
   // one copy of the stream (a piecewise upload on a second stream, each piece
   // verified as it landed, measured slower on the 512-group ingest workload:
   // 3.57 against 3.26 ms per round; the walk cannot start before the last piece)
-  HIP_OK(hipMemcpyAsync(e->wire_in, data, bytes, hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(k_wire_verify, dim3((unsigned)nf), dim3(256), 0, e->stream, e->wire_in, dfr,
+  HIP_OK(hipMemcpyAsync(e->wire_in.p(), data, bytes, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_wire_verify, dim3((unsigned)nf), dim3(256), 0, e->stream, e->wire_in.p(), dfr,
                      0u, big);
   // one block per frame: its walk is a chain of LDS reads (~0.2 ms for an
   // 18 KB frame) whatever the grid
   hipLaunchKernelGGL(k_wire_bounds, dim3((unsigned)nf), dim3(kWireWalkBlock), 0, e->stream,
-                     e->wire_in, dfr, 2, spos, big, 0u);
+                     e->wire_in.p(), dfr, 2, spos, big, 0u);
   if (nbig) {
-    hipLaunchKernelGGL(k_wire_chunk_crc, dim3((unsigned)nseg), dim3(256), 0, e->stream, e->wire_in,
+    hipLaunchKernelGGL(k_wire_chunk_crc, dim3((unsigned)nseg), dim3(256), 0, e->stream, e->wire_in.p(),
                        dfr, dseg);
     hipLaunchKernelGGL(k_wire_crc_check, dim3((unsigned)((nbig + 63) / 64)), dim3(64), 0,
                        e->stream, dfr, dbig, (u32)nbig);
     hipLaunchKernelGGL(k_wire_chunk_exit, dim3((unsigned)nch), dim3(256), 0, e->stream,
-                       e->wire_in, dfr, dch, exitv, cntv);
+                       e->wire_in.p(), dfr, dch, exitv, cntv);
     hipLaunchKernelGGL(k_wire_hop, dim3((unsigned)nbig), dim3(64), 0, e->stream, dfr, dbig, dch0,
                        exitv, cntv, ent, cbase);
-    hipLaunchKernelGGL(k_wire_chunk_emit, dim3((unsigned)nch), dim3(64), 0, e->stream, e->wire_in,
+    hipLaunchKernelGGL(k_wire_chunk_emit, dim3((unsigned)nch), dim3(64), 0, e->stream, e->wire_in.p(),
                        dfr, dch, ent, cbase, 2, spos);
   }
   HIP_OK(hipGetLastError());
@@ -3851,9 +3716,9 @@ static int wire_decode_dev(rbe_engine* e, const void* data, uint64_t bytes, Wire
   const u64 o_ec = al(tm * sizeof(WireMsgPos)), o_cc = o_ec + al(tm * 8), o_t1 = o_cc + al(tm * 8);
   const u64 o_t2 = o_t1 + al((nbk + 1) * 8), o_err = o_t2 + al((nbk + 1) * 8);
   const u64 o_rec = o_err + 256;
-  rc = grow(&e->wire_rec, &e->wire_rec_bytes, o_rec, false);
+  rc = e->wire_rec.reserve(o_rec);
   if (rc) return rc;
-  u8* w = e->wire_rec;
+  u8* w = e->wire_rec.p();
   WireMsgPos* pos = (WireMsgPos*)w;
   u64 *ec = (u64*)(w + o_ec), *cc = (u64*)(w + o_cc), *t1 = (u64*)(w + o_t1), *t2 = (u64*)(w + o_t2);
   u32* err = (u32*)(w + o_err);
@@ -3861,16 +3726,16 @@ static int wire_decode_dev(rbe_engine* e, const void* data, uint64_t bytes, Wire
   HIP_OK(hipMemsetAsync(err, 0, 4, e->stream));
   if (refill) {
     hipLaunchKernelGGL(k_wire_bounds, dim3((unsigned)nf), dim3(kWireWalkBlock), 0, e->stream,
-                       e->wire_in, dfr, 1, pos, big, 0u);
+                       e->wire_in.p(), dfr, 1, pos, big, 0u);
     if (nch)
       hipLaunchKernelGGL(k_wire_chunk_emit, dim3((unsigned)nch), dim3(64), 0, e->stream,
-                         e->wire_in, dfr, wf.dch, wf.ent, wf.cbase, 1, pos);
+                         e->wire_in.p(), dfr, wf.dch, wf.ent, wf.cbase, 1, pos);
   } else
     hipLaunchKernelGGL(k_wire_compact, dim3((unsigned)nf, wf.compact_y), dim3(256), 0, e->stream,
                        dfr, spos, pos, ~0ull);
   const unsigned gm = (unsigned)nbk;
   if (tm) {
-    hipLaunchKernelGGL(k_wire_parse, dim3(gm), dim3(256), 0, e->stream, e->wire_in, pos, tm, 0,
+    hipLaunchKernelGGL(k_wire_parse, dim3(gm), dim3(256), 0, e->stream, e->wire_in.p(), pos, tm, 0,
                        ec, cc, nullptr, nullptr, nullptr, err);
     hipLaunchKernelGGL(k_scan_blocks, dim3(gm), dim3(256), 0, e->stream, ec, tm, t1);
     hipLaunchKernelGGL(k_scan_blocks, dim3(gm), dim3(256), 0, e->stream, cc, tm, t2);
@@ -3895,20 +3760,9 @@ static int wire_decode_dev(rbe_engine* e, const void* data, uint64_t bytes, Wire
   if (caps && (tm > caps[0] || te > caps[1] || tc > caps[2])) return RBE_E_NOMEM;
   const u64 o_m = o_rec, o_e = o_m + al(tm * sizeof(rbe_message)),
             o_c = o_e + al(te * sizeof(rbe_entry));
-  {
-    // keep the scratch above while growing (a fresh buffer only when short)
-    const u64 need = o_c + al(tc) + 256;
-    if (need > e->wire_rec_bytes) {
-      u8* nb = nullptr;
-      HIP_OK(hipMalloc((void**)&nb, need + need / 2));
-      HIP_OK(hipMemcpyAsync(nb, e->wire_rec, o_rec, hipMemcpyDeviceToDevice, e->stream));
-      HIP_OK(hipStreamSynchronize(e->stream));
-      HIP_OK(hipFree(e->wire_rec));
-      e->wire_rec = nb;
-      e->wire_rec_bytes = need + need / 2;
-    }
-  }
-  w = e->wire_rec;
+  // keep the scratch above while growing (a fresh buffer only when short)
+  if ((rc = e->wire_rec.reserve_keep(o_c + al(tc) + 256, o_rec, e->stream))) return rc;
+  w = e->wire_rec.p();
   pos = (WireMsgPos*)w;
   ec = (u64*)(w + o_ec);
   cc = (u64*)(w + o_cc);
@@ -3917,7 +3771,7 @@ static int wire_decode_dev(rbe_engine* e, const void* data, uint64_t bytes, Wire
   rbe_entry* de = (rbe_entry*)(w + o_e);
   u8* dc = w + o_c;
   if (tm)
-    hipLaunchKernelGGL(k_wire_parse, dim3(gm), dim3(256), 0, e->stream, e->wire_in, pos, tm, 1,
+    hipLaunchKernelGGL(k_wire_parse, dim3(gm), dim3(256), 0, e->stream, e->wire_in.p(), pos, tm, 1,
                        ec, cc, dm, de, dc, err);
   HIP_OK(hipGetLastError());
   o->msgs = dm;
@@ -3977,8 +3831,8 @@ static int wire_ingest_fast(rbe_engine* e, const void* data, uint64_t bytes,
   const u64 o_t2 = o_t1 + al((nbk + 1) * 8), o_tot = o_t2 + al((nbk + 1) * 8);
   const u64 o_m = o_tot + 256, o_e = o_m + al(cm * sizeof(rbe_message));
   const u64 o_c = o_e + al(ce * sizeof(rbe_entry)), need_rec = o_c + al(cc) + 256;
-  if ((rc = grow(&e->wire_rec, &e->wire_rec_bytes, need_rec, false))) return rc;
-  u8* w = e->wire_rec;
+  if ((rc = e->wire_rec.reserve(need_rec))) return rc;
+  u8* w = e->wire_rec.p();
   WireMsgPos* pos = (WireMsgPos*)w;
   u64 *ec = (u64*)(w + o_ec), *ccn = (u64*)(w + o_cc), *t1 = (u64*)(w + o_t1), *t2 = (u64*)(w + o_t2);
   u64* tot = (u64*)(w + o_tot);
@@ -3995,8 +3849,8 @@ static int wire_ingest_fast(rbe_engine* e, const void* data, uint64_t bytes,
   const u64 o_sk = al(cm * 8), o_hb = o_sk + al(cm * 8), o_hs = o_hb + al(cm * 8);
   const u64 o_ix = o_hs + al(cm * 8), o_si = o_ix + al(cm * 4), o_top = o_si + al(cm * 4);
   const u64 o_err = o_top + al((nbk + 1) * 8), o_tmp = o_err + 256;
-  if ((rc = grow(&e->ing_dev, &e->ing_dev_bytes, o_tmp + al(tb), false))) return rc;
-  u8* b = e->ing_dev;
+  if ((rc = e->ing_dev.reserve(o_tmp + al(tb)))) return rc;
+  u8* b = e->ing_dev.p();
   u64 *key = (u64*)b, *skey = (u64*)(b + o_sk), *hb = (u64*)(b + o_hb), *hs = (u64*)(b + o_hs);
   u32 *idx = (u32*)(b + o_ix), *sidx = (u32*)(b + o_si);
   u64* top = (u64*)(b + o_top);
@@ -4009,7 +3863,7 @@ static int wire_ingest_fast(rbe_engine* e, const void* data, uint64_t bytes,
                      tot, dfl);
   hipLaunchKernelGGL(k_wire_compact, dim3((unsigned)nf, wf.compact_y), dim3(256), 0, e->stream,
                      wf.dfr, wf.spos, pos, cm);
-  hipLaunchKernelGGL(k_wire_parse, dim3(g), dim3(256), 0, e->stream, e->wire_in, pos, cm, 0, ec,
+  hipLaunchKernelGGL(k_wire_parse, dim3(g), dim3(256), 0, e->stream, e->wire_in.p(), pos, cm, 0, ec,
                      ccn, nullptr, nullptr, nullptr, dfl, tot, nullptr, nullptr, 0ull, 0ull, dfl);
   hipLaunchKernelGGL(k_scan_blocks, dim3(g), dim3(256), 0, e->stream, ec, cm, t1);
   hipLaunchKernelGGL(k_scan_blocks, dim3(g), dim3(256), 0, e->stream, ccn, cm, t2);
@@ -4017,7 +3871,7 @@ static int wire_ingest_fast(rbe_engine* e, const void* data, uint64_t bytes,
   hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, e->stream, t2, (u32)nbk);
   hipLaunchKernelGGL(k_scan_add, dim3(g), dim3(256), 0, e->stream, ec, cm, t1);
   hipLaunchKernelGGL(k_scan_add, dim3(g), dim3(256), 0, e->stream, ccn, cm, t2);
-  hipLaunchKernelGGL(k_wire_parse, dim3(g), dim3(256), 0, e->stream, e->wire_in, pos, cm, 1, ec,
+  hipLaunchKernelGGL(k_wire_parse, dim3(g), dim3(256), 0, e->stream, e->wire_in.p(), pos, cm, 1, ec,
                      ccn, dm, de, dc, dfl, tot, t1 + nbk, t2 + nbk, ce, cc, dfl);
   const u32 par = (e->round - 1) & 1u;
   rc = dispatch_n(C.n, [&](auto NN) {
@@ -4116,8 +3970,8 @@ int rbe_wire_ingest(rbe_engine* e, const void* data, uint64_t bytes, rbe_wire_in
   const u64 o_sk = al(tm * 8), o_hb = o_sk + al(tm * 8), o_hs = o_hb + al(tm * 8);
   const u64 o_ix = o_hs + al(tm * 8), o_si = o_ix + al(tm * 4), o_top = o_si + al(tm * 4);
   const u64 o_err = o_top + al((nbk + 1) * 8), o_tmp = o_err + 256;
-  if ((rc = grow(&e->ing_dev, &e->ing_dev_bytes, o_tmp + al(tb), false))) return rc;
-  u8* b = e->ing_dev;
+  if ((rc = e->ing_dev.reserve(o_tmp + al(tb)))) return rc;
+  u8* b = e->ing_dev.p();
   u64 *key = (u64*)b, *skey = (u64*)(b + o_sk), *hb = (u64*)(b + o_hb), *hs = (u64*)(b + o_hs);
   u32 *idx = (u32*)(b + o_ix), *sidx = (u32*)(b + o_si);
   u64* top = (u64*)(b + o_top);
@@ -4208,17 +4062,17 @@ int rbe_iso_leaders(rbe_engine* e, uint8_t* out, uint32_t* epoch) {
   *epoch = C.iso_period && e->round > 0 && e->round % C.iso_period == 0 ? 1u : 0u;
   if (!*epoch || !out) return RBE_OK;
   HIP_OK(hipSetDevice(e->device));
-  if (!e->iso_dev) HIP_OK(hipMalloc((void**)&e->iso_dev, C.n_groups_glob));
-  HIP_OK(hipMemsetAsync(e->iso_dev, 0, C.n_groups_glob, e->stream));
+  if (e->iso_dev.reserve_cap(C.n_groups_glob, C.n_groups_glob)) return RBE_E_HIP;
+  HIP_OK(hipMemsetAsync(e->iso_dev.p(), 0, C.n_groups_glob, e->stream));
   const int rc = dispatch_n(C.n, [&](auto NN) {
     constexpr int N = decltype(NN)::value;
     hipLaunchKernelGGL(k_iso_bits<N>, dim3(grid_for(C.n_groups)), dim3(kBlock), 0, e->stream,
-                       e->P, e->C, e->iso_dev);
+                       e->P, e->C, e->iso_dev.p());
     HIP_OK(hipGetLastError());
     return RBE_OK;
   });
   if (rc) return rc;
-  HIP_OK(hipMemcpyAsync(out, e->iso_dev, C.n_groups_glob, hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipMemcpyAsync(out, e->iso_dev.p(), C.n_groups_glob, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
   return RBE_OK;
 }
@@ -4228,8 +4082,8 @@ int rbe_set_iso_leaders(rbe_engine* e, const uint8_t* bits) {
   const Params& C = e->C;
   if (!(C.iso_period && e->round > 0 && e->round % C.iso_period == 0)) return RBE_E_STATE;
   HIP_OK(hipSetDevice(e->device));
-  if (!e->iso_dev) HIP_OK(hipMalloc((void**)&e->iso_dev, C.n_groups_glob));
-  HIP_OK(hipMemcpyAsync(e->iso_dev, bits, C.n_groups_glob, hipMemcpyHostToDevice, e->stream));
+  if (e->iso_dev.reserve_cap(C.n_groups_glob, C.n_groups_glob)) return RBE_E_HIP;
+  HIP_OK(hipMemcpyAsync(e->iso_dev.p(), bits, C.n_groups_glob, hipMemcpyHostToDevice, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
   e->iso_round = e->round;
   return RBE_OK;

@@ -31,6 +31,34 @@ namespace rbe {
     }                                                                  \
   } while (0)
 
+// The kinds of memory a Scratch owns (rbe_scratch.h): device, pinned host, and
+// pinned host mapped into the device's address space
+struct MemCopy {
+  static int copy(void* dst, const void* src, u64 n, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (n) HIP_OK(hipMemcpyAsync(dst, src, n, hipMemcpyDefault, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return RBE_OK;
+  }
+};
+struct DevMem : MemCopy {
+  static int alloc(void** p, u64 n) {
+    HIP_OK(hipMalloc(p, n));
+    return RBE_OK;
+  }
+  static void free(void* p) { HIP_IGNORE(hipFree(p)); }
+};
+template <unsigned kFlags>
+struct HostMem : MemCopy {
+  static int alloc(void** p, u64 n) {
+    HIP_OK(hipHostMalloc(p, n, kFlags));
+    return RBE_OK;
+  }
+  static void free(void* p) { HIP_IGNORE(hipHostFree(p)); }
+};
+using PinnedMem = HostMem<hipHostMallocDefault>;
+using MappedMem = HostMem<hipHostMallocMapped>;
+
 static constexpr int kBlock = 256;
 // minimum waves per SIMD requested for the fast-step kernels (caps their VGPRs:
 // 2 -> 256, 3 -> 168, 4 -> 128; beyond the cap the compiler spills to scratch)
