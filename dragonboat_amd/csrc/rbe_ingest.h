@@ -71,7 +71,7 @@ RBE_HD void ingest_ids(const Params& C, const u64* ids, rbe_message& m) {
 // cid_stride, as every engine API names it).
 template <int N>
 RBE_HD u64 ingest_check(const Params& C, u64 heap_cap, const rbe_message& m, const rbe_entry* ents,
-                        u32* err, u64* heap) {
+                        u32* err, u64* heap, bool spill = false) {
   *heap = 0;
   const u64 drop = ing_drop_key(C);
   if (m.type >= 26 || is_local_message(m.type)) {  // a local type is a caller bug (panics)
@@ -98,7 +98,9 @@ RBE_HD u64 ingest_check(const Params& C, u64 heap_cap, const rbe_message& m, con
     *err |= ING_INVALID;
     return drop;
   }
-  if (m.n_entries > 0xFFFFu || m.n_entries > C.ecap) {
+  // (`spill`: the caller keeps entries past the arena in the round spill heap,
+  // rbe_ingest_spill.h; rbe_wire_ingest does not yet)
+  if (!spill && (m.n_entries > 0xFFFFu || m.n_entries > C.ecap)) {
     *err |= ING_NOMEM;
     return drop;
   }

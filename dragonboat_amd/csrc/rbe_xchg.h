@@ -304,23 +304,45 @@ int outbox_messages(const Params& C, u64 g, u32 k, const CntRow& row, u32 round,
 // stamped for `round` (the round that reads them); a sender not named keeps a
 // stale header, which reads as empty.  Checked whole before anything is
 // staged: RBE_OK, RBE_E_INVALID (ids, ownership, entry indexes or types) or
-// RBE_E_NOMEM (more than maxm messages in one list, more than ecap entries
-// from one sender, or no heap room).
+// RBE_E_NOMEM (no heap room; without `sp` also more than maxm messages in one
+// list or more than ecap entries from one sender).
+//
+// With `sp` (granules of this engine's share of the round spill heap, reserved
+// by the caller between two rounds) a list past maxm and a message's entries
+// past the sender's arena row go to the spill heap in the exchange's own record
+// form (xchg_sender): the M_SpillRef header at plane slot 0 and XMsg{slot =
+// kXSpill | granule} per message, XEnt{off = kXSpill | granule} per entry.  The
+// granules follow the placement rule of rbe_ingest_spill.h ingest_sender_spill: senders in
+// ascending order, per sender its spilled lists by ascending destination, then
+// the spilled messages' entries by destination and stream order; sp->total gets
+// their number, and more than sp->avail is RBE_E_NOMEM with nothing staged.
+struct XSpillRes {
+  u64 base;   // in: first free granule of this engine's share (share * rank + used)
+  u64 avail;  // in: free granules of the share
+  u64 total;  // out: granules the batch took
+};
 template <int N>
 int messages_to_records(const Params& C, HostHeap& heap, u32 round, u64 n, const u64* group,
                         const rbe_message* msgs, const rbe_entry* ents, const u8* cmd,
                         std::vector<XCnt>& oc, std::vector<XMsg>& om, std::vector<XEnt>& oe,
-                        const u64* ids = nullptr) {
+                        const u64* ids = nullptr, XSpillRes* sp = nullptr) {
   u64 total = 0;
   for (u64 i = 0; i < n; i++) total += msgs[i].n_entries;
   if (total && !ents) return RBE_E_INVALID;
   u64 need = 0;
   int rc = check_entries(heap, total, ents, cmd, true, &need);
   if (rc) return rc;
+  struct List {
+    u32 na = 0, nb = 0, q = 0;  // messages placed so far, the Quiesce notice
+    u32 ta = 0, tb = 0;         // the list's totals (the counting pass)
+    u64 gran = 0;               // its block, when ta + tb > maxm
+  };
+  std::unordered_map<u64, List> lists;  // list key → its state
+  std::vector<u64> order;               // list keys in first-use order
+  std::vector<u64> xgran(sp ? n : 0, 0);  // message → granule of its spilled entries
+  std::vector<u8> xe(sp ? n : 0, 0);      // message → its entries are spilled
   auto pass = [&](bool write) -> int {
-    std::unordered_map<u64, u32> words;  // list key → count word
-    std::vector<u64> order;              // list keys in first-use order
-    std::unordered_map<u64, u32> used;   // sender replica → arena entries used
+    std::unordered_map<u64, u32> used;  // sender replica → arena entries used
     u64 ei = 0, coff = 0;
     for (u64 i = 0; i < n; i++) {
       rbe_message m = msgs[i];
@@ -342,21 +364,21 @@ int messages_to_records(const Params& C, HostHeap& heap, u32 round, u64 n, const
       if (owner_of<N>(C, g, s) == C.rep_rank || owner_of<N>(C, g, d) != C.rep_rank)
         return RBE_E_INVALID;
       const u64 key = (group_global(C, g) * N + s) * N + d;  // records carry global indexes
-      auto it = words.find(key);
-      if (it == words.end()) {
-        it = words.emplace(key, 0u).first;
+      auto it = lists.find(key);
+      if (it == lists.end()) {
+        it = lists.emplace(key, List()).first;
         order.push_back(key);
       }
-      u32& w = it->second;
+      List& l = it->second;
       if (m.type == M_Quiesce) {
         if (m.n_entries) return RBE_E_INVALID;
-        w |= 0x8000u;
+        l.q = 1;
         continue;
       }
       const bool with_ents = m.type == M_Replicate || m.type == M_Propose;
       if (m.n_entries && !with_ents) return RBE_E_INVALID;
-      const u32 na = w & 0x7Fu, nb = (w >> 7) & 0x7Fu;
-      if (na + nb >= C.maxm) return RBE_E_NOMEM;
+      const bool spl = write && l.ta + l.tb > C.maxm;
+      if (!sp && l.na + l.nb >= C.maxm) return RBE_E_NOMEM;
       XMsg x;
       x.key = key;
       x.m = mk_msg(m.type, m.to);
@@ -374,19 +396,23 @@ int messages_to_records(const Params& C, HostHeap& heap, u32 round, u64 n, const
         x.m.pad0 = (u16)(m.reserved & 0xFFu);
         x.m.pad1 = (m.reserved >> 8) & 0xFFFFu;
       }
-      if (m.type == M_Replicate) {
-        x.slot = na;
-        w += 1u;
-      } else {
-        x.slot = C.maxm - 1u - nb;
-        w += 1u << 7;
-      }
+      u32 bi;  // index in the list's block (the plane's, or its spill heap block's)
+      if (m.type == M_Replicate) bi = l.na++;
+      else bi = (spl ? l.ta + l.tb : C.maxm) - 1u - l.nb++;
+      x.slot = spl ? kXSpill | (l.gran + (u64)bi * (sizeof(Msg) / 16)) : bi;
       if (with_ents && m.n_entries) {
         const u64 sr = group_global(C, g) * N + s;
         u32& off = used[sr];
-        if (m.n_entries > 0xFFFFu || off + m.n_entries > C.ecap) return RBE_E_NOMEM;
-        x.m.n_ent = (u16)m.n_entries;
+        const bool over = (u64)off + m.n_entries > C.ecap;
+        if (!sp && (m.n_entries > 0xFFFFu || over)) return RBE_E_NOMEM;
+        if (sp && !write) xe[i] = over ? 1 : 0;
+        x.m.n_ent = (u16)(m.n_entries > 0xFFFFu ? 0xFFFFu : m.n_entries);
         x.m.ent_off = off;
+        if (over) {  // (Lane::set_ents)
+          x.m.pad0 |= kMsgXEnt;
+          x.m.pad1 = m.n_entries;
+          x.m.ent_off = (u32)xgran[i];
+        }
         for (u32 j = 0; j < m.n_entries; j++, ei++) {
           const rbe_entry& e = ents[ei];
           if (m.type == M_Replicate && e.index != m.log_index + 1 + j) return RBE_E_INVALID;
@@ -395,15 +421,23 @@ int messages_to_records(const Params& C, HostHeap& heap, u32 round, u64 n, const
           if (!write) continue;
           XEnt y;
           y.key = sr;
-          y.off = off + j;
+          y.off = over ? kXSpill | (xgran[i] + (u64)j * (sizeof(Ent) / 16)) : off + j;
           y.e = stage_entry(heap, e, cb);
           oe.push_back(y);
         }
-        off += m.n_entries;
+        if (!over) off += m.n_entries;
       }
       if (write) om.push_back(x);
     }
-    if (!write) return RBE_OK;
+    if (!write) {
+      for (auto& kv : lists) {  // the totals; the writing pass counts again
+        List& l = kv.second;
+        l.ta = l.na;
+        l.tb = l.nb;
+        l.na = l.nb = 0;
+      }
+      return RBE_OK;
+    }
     // one stamped header per sender with the words of all its lists
     std::unordered_map<u64, size_t> hdr;  // sender replica → index in oc
     for (u64 key : order) {
@@ -419,11 +453,66 @@ int messages_to_records(const Params& C, HostHeap& heap, u32 round, u64 n, const
         it = hdr.emplace(sr, oc.size()).first;
         oc.push_back(c);
       }
-      oc[it->second].row.w[cnt_widx(d, (u32)(sr % N))] = (u16)words[key];
+      const List& l = lists[key];
+      u32 word = l.na | (l.nb << 7);
+      if (l.ta + l.tb > C.maxm) {  // the plane slot 0 redirect record (outbox_relocate)
+        word = kCntSpilled;
+        XMsg x;
+        x.key = key;
+        x.slot = 0;
+        x.m = Msg{};
+        x.m.type = M_SpillRef;
+        x.m.hint = l.gran;
+        x.m.pad1 = l.ta + l.tb;
+        x.m.log_index = l.ta;
+        x.m.commit = l.tb;
+        om.push_back(x);
+      }
+      oc[it->second].row.w[cnt_widx(d, (u32)(sr % N))] = (u16)(word | (l.q ? kCntQ : 0u));
     }
     return RBE_OK;
   };
   if ((rc = pass(false))) return rc;
+  if (sp) {
+    // the placement: senders ascending; per sender the spilled lists by
+    // ascending destination, then the spilled messages' entries by destination
+    // and stream order (the order of ingest_sender's sorted run)
+    std::vector<u64> keys;
+    for (auto& kv : lists) keys.push_back(kv.first);
+    std::sort(keys.begin(), keys.end());
+    std::unordered_map<u64, std::vector<u64>> xmsgs;  // list key → messages with spilled entries
+    for (u64 i = 0; i < n; i++) {
+      if (!xe[i]) continue;
+      rbe_message m = msgs[i];
+      if (ids) {
+        m.from = int_id<N>(ids, group[i], m.from);
+        m.to = int_id<N>(ids, group[i], m.to);
+      }
+      xmsgs[(group_global(C, group[i]) * N + (m.from - 1)) * N + (m.to - 1)].push_back(i);
+    }
+    u64 cur = sp->base;
+    for (size_t a = 0; a < keys.size();) {
+      size_t b = a;
+      while (b < keys.size() && keys[b] / N == keys[a] / N) b++;
+      for (size_t k = a; k < b; k++) {
+        List& l = lists[keys[k]];
+        if (l.ta + l.tb <= C.maxm) continue;
+        l.gran = cur;
+        cur += (u64)(l.ta + l.tb) * (sizeof(Msg) / 16);
+      }
+      for (size_t k = a; k < b; k++) {
+        auto it = xmsgs.find(keys[k]);
+        if (it == xmsgs.end()) continue;
+        for (u64 i : it->second) {
+          xgran[i] = cur;
+          cur += (u64)msgs[i].n_entries * (sizeof(Ent) / 16);
+        }
+      }
+      a = b;
+    }
+    sp->total = cur - sp->base;
+    if (sp->total > sp->avail) return RBE_E_NOMEM;
+  }
   if (need && (rc = heap.room(need))) return rc;
   return pass(true);
 }
