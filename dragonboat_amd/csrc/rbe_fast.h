@@ -97,6 +97,32 @@ struct FastCaps {
   static constexpr u32 RQ = 3;                 // readIndex queue entries in registers
 };
 
+// The speculative inbound gathers.  With the summary-word form (AUX) the
+// message loads of a fast step issue before the step checks that it takes the
+// round, from counts that may be the clamp of anything: a list in the round
+// spill heap has the count word kCntSpilled and the summary field A = B = 7,
+// whatever maxm is.  These two functions say whether gather slot i loads and
+// from which slot of the sender's list, and no slot that loads lies outside
+// [0, maxm): a count the step declines anyway, or one no list of maxm slots
+// can hold, loads nothing.  For the counts a step accepts they give the slots
+// the lists are written to (A messages up from slot 0, B messages down from
+// slot maxm - 1).  tests/fast_aux_cpu walks every summary field and maxm.
+//
+// lead_fast: slot i (< MAXM) of the sender whose count word is pc
+template <int N>
+RBE_HD bool lead_gather_slot(u32 pc, u32 maxm, u32 i, u32& at) {
+  const u32 na = pc & 0x7Fu, nb = (pc >> 7) & 0x7Fu;
+  at = maxm - 1u - i;
+  return na == 0 && nb <= FastCaps<N>::MAXM && nb <= maxm && i < nb;
+}
+// foll_fast: slot i (< FMAXM) of the one sender with messages
+template <int N>
+RBE_HD bool foll_gather_slot(u32 pc, u32 maxm, u32 i, u32& at) {
+  const u32 na = pc & 0x7Fu, n = na + ((pc >> 7) & 0x7Fu);
+  at = i < na ? i : maxm - 1u - (i - na);
+  return n <= FastCaps<N>::FMAXM && n <= maxm && i < n;
+}
+
 // one inbound message, the fields a steady-state handler reads
 struct InMsg {
   u32 type, reject, n_ent, ent_off;
@@ -598,6 +624,9 @@ RBE_HD bool lead_fast(const Planes& P, const Params& C, u64 r, const Clk& ck, CT
   // for the lane's own slot, which is what keeps the step out of scratch.
   // With AUX the counts are known before any load, so the inbound messages
   // are part of the first gather level; otherwise they wait for the counts.
+  // The loads come before the eligibility checks then, so a count the step
+  // declines below (a spilled list's among them) loads nothing, and no load
+  // leaves the list (lead_gather_slot).
   LeadMsg in[N - 1][Cap::MAXM];
   auto load_inbox = [&]() {
 #pragma unroll
@@ -607,13 +636,13 @@ RBE_HD bool lead_fast(const Planes& P, const Params& C, u64 r, const Clk& ck, CT
 #pragma unroll
       for (u32 t = 0; t < N; t++)
         if (t == sj) pj = pcin[t];
-      const u32 nbj = (pj >> 7) & 0x7Fu;
       const Msg* lst = &P.msgs[ppar][((g * N + sj) * N + k) * (u64)C.maxm];
 #pragma unroll
       for (u32 i = 0; i < Cap::MAXM; i++) {
         in[j][i].w = 0xFFu;
         in[j][i].term = in[j][i].log_index = in[j][i].hint = in[j][i].hint_high = 0;
-        if (i < nbj) in[j][i] = load_lead(&lst[C.maxm - 1u - i]);
+        u32 at;
+        if (lead_gather_slot<N>(pj, C.maxm, i, at)) in[j][i] = load_lead(&lst[at]);
       }
     }
   };
@@ -1397,24 +1426,27 @@ RBE_HD bool foll_fast(const Planes& P, const Params& C, u64 r, const Clk& ck, CT
   if constexpr (AUX) {
 #pragma unroll
     for (u32 s = 0; s < N; s++) pcin[s] = s == k ? 0u : aux_count_word<N>(aux, k, s);
-    u32 na_a = 0, n_a = 0;
+    u32 pc_a = 0;  // the count word of the lowest sender that has messages
 #pragma unroll
     for (u32 s = N; s-- > 0;) {
       const u32 n = (pcin[s] & 0x7Fu) + ((pcin[s] >> 7) & 0x7Fu);
       if (s != k && n) {
         ls_a = s;
-        na_a = pcin[s] & 0x7Fu;
-        n_a = n;
+        pc_a = pcin[s];
       }
     }
     const u32 sa = ls_a < N ? ls_a : 0u;
     const Msg* la = &P.msgs[ppar][((g * N + sa) * N + k) * (u64)C.maxm];
+    // (a count the step declines below, a spilled list's among them, loads
+    // nothing: foll_gather_slot)
 #pragma unroll
-    for (u32 i = 0; i < Cap::FMAXM; i++)
-      if (i < n_a) raw[i] = la[i < na_a ? i : C.maxm - 1u - (i - na_a)];
+    for (u32 i = 0; i < Cap::FMAXM; i++) {
+      u32 at;
+      if (foll_gather_slot<N>(pc_a, C.maxm, i, at)) raw[i] = la[at];
+    }
     spec0.term = spec0.lo = spec0.hi = 0;
     spec0.type = spec0.len = 0;
-    if (na_a > 0) spec0 = P.arena[ppar][(g * N + sa) * (u64)C.ecap];
+    if ((pc_a & 0x7Fu) > 0) spec0 = P.arena[ppar][(g * N + sa) * (u64)C.ecap];
   } else {
 #pragma unroll
     for (u32 s = 0; s < N; s++) pcin[s] = s != k ? in_word<N>(P, g, s, k, round) : 0u;
@@ -1434,8 +1466,6 @@ RBE_HD bool foll_fast(const Planes& P, const Params& C, u64 r, const Clk& ck, CT
   if (!ck.tick) return false;
   if (C.xfer_period && xfer_input(C, cid_of_n<N>(C, g), round, k)) return false;
   if (C.ext_inputs && P.ext[r].flags) return false;
-  // the step's ReadyToReads (one per ReadIndexResp) stay within the plane list
-  if (C.rtr_cap < Cap::FMAXM) return false;
   const u32 ls = (u32)c.leader - 1u;  // leader slot (0xFFFFFFFF when no leader)
   u32 n_in = 0;
 #pragma unroll
@@ -1446,6 +1476,9 @@ RBE_HD bool foll_fast(const Planes& P, const Params& C, u64 r, const Clk& ck, CT
     n_in += n;
   }
   if (n_in > Cap::FMAXM) return false;
+  // the step's ReadyToReads (one per ReadIndexResp, so at most n_in) stay
+  // within the plane list
+  if (n_in > C.rtr_cap) return false;
   // ---- gather, level 2: the leader's messages (Replicate first, then the rest)
   RBE_STAMP(t1);
   InMsg in[Cap::FMAXM];

@@ -422,7 +422,11 @@ RBE_HD void spill_clear_next(const Planes& P, u32 par) { P.sctl->used[par ^ 1u] 
 // count word bits (CntRow::w): A | B << 7 | kCntSpill | quiesce << 15
 static constexpr u32 kCntSpill = 0x4000u;
 static constexpr u32 kCntQ = 0x8000u;
-// a spilled list's count word (saturated counts: every fast step declines it)
+// a spilled list's count word: saturated counts (7 / 7 in the summary word,
+// inbound_aux), which every fast step declines.  With the summary word it
+// declines after its speculative gather, which must not take them for a
+// length (the plane list has maxm slots, whatever the counts say): the gathers
+// load no slot for them (rbe_fast.h lead_gather_slot / foll_gather_slot)
 static constexpr u32 kCntSpilled = 0x7Fu | (0x7Fu << 7) | kCntSpill;
 // message type of the record a spilled list leaves in its plane slot 0
 // (hint = the list's granule in the spill heap, pad1 = its capacity,

@@ -3856,7 +3856,12 @@ RBE_HD u32 inbound_bits(const Planes& P, u64 r, u32 round) {
 // loading them, so their message loads issue in the first gather level.  The
 // clamp keeps every decision the fast steps take on the words: a leader
 // declines A > 0 or B > MAXM (< 7), a follower more than FMAXM (< 7) inbound
-// messages, and every count that is used is below 7.
+// messages, so every count of a round they accept is below 7 and exact.  A
+// clamped count says nothing about the list's length, though (a spilled
+// list's word, kCntSpilled, gives A = B = 7 at any maxm), and the message
+// loads issue before the step has declined: the gathers take no slot from a
+// count the step declines or maxm cannot hold (rbe_fast.h lead_gather_slot /
+// foll_gather_slot).
 template <int N>
 RBE_HD u32 inbound_aux(const u16 (&w)[N], u32 k, u32 round) {
   u32 aux = 0;
