@@ -799,6 +799,9 @@ struct rbe_engine {
   // capacities the no-read-back ingest launches for (messages, entries, Cmd
   // bytes): the last call's counts + 25%; 0 until a call has measured them
   u64 ing_cap[3] = {0, 0, 0};
+  // rbe_inbound_spill_stats: bytes of the round spill heap the inbound batches
+  // took (cumulative), batches that spilled, batches refused for a short share
+  u64 in_spill[3] = {0, 0, 0};
   // rbe_collect_updates: the same for the compacted Updates
   Scratch<DevMem> upd_dev;
   Scratch<PinnedMem> upd_host;
@@ -2486,6 +2489,13 @@ static int xchg_scatter(rbe_engine* e, const void* cnt, uint64_t n_cnt, const vo
   return RBE_OK;
 }
 
+// rbe_inbound_spill_stats: a batch took `granules` of the round spill heap
+static void note_inbound_spill(rbe_engine* e, u64 granules) {
+  if (!granules) return;
+  e->in_spill[0] += granules * 16;
+  e->in_spill[1]++;
+}
+
 int rbe_xchg_unpack(rbe_engine* e, const void* cnt, uint64_t n_cnt, const void* msg, uint64_t n_msg,
                     const void* ent, uint64_t n_ent) {
   if (!e || e->round == 0) return RBE_E_INVALID;
@@ -2551,11 +2561,21 @@ int rbe_push_messages(rbe_engine* e, uint64_t n, const uint64_t* group, const rb
   std::vector<XCnt> c;
   std::vector<XMsg> m;
   std::vector<XEnt> x;
+  // what is left of this engine's share of the last round's spill heap: lists
+  // past maxm and entries past ecap go there (rbe_ingest_spill.h)
+  const u32 par = (e->round - 1) & 1u;
+  u64 used = 0;
+  HIP_OK(hipMemcpyAsync(&used, &e->P.sctl->used[par], sizeof(u64), hipMemcpyDeviceToHost,
+                        e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  const u64 share = spill_share(e->C);
+  XSpillRes sp{share * e->C.rep_rank + used, used < share ? share - used : 0, 0};
   int rc = dispatch_n(e->C.n, [&](auto NN) {
     constexpr int N = decltype(NN)::value;
     return messages_to_records<N>(e->C, e->hin.heap, e->round, n, group, msgs, ents, cmd, c, m,
-                                  x, e->hin.id_table());
+                                  x, e->hin.id_table(), &sp);
   });
+  if (rc == RBE_E_NOMEM && sp.total > sp.avail) e->in_spill[2]++;
   if (rc) return rc;
   const size_t bytes = c.size() * sizeof(XCnt) + m.size() * sizeof(XMsg) + x.size() * sizeof(XEnt);
   Scratch<DevMem> tmp;  // freed on every return below
@@ -2567,7 +2587,17 @@ int rbe_push_messages(rbe_engine* e, uint64_t n, const uint64_t* group, const rb
     HIP_OK(hipMemcpyAsync(d + om, m.data(), ox - om, hipMemcpyHostToDevice, e->stream));
   if (!x.empty())
     HIP_OK(hipMemcpyAsync(d + ox, x.data(), bytes - ox, hipMemcpyHostToDevice, e->stream));
-  return xchg_scatter(e, d, c.size(), d + om, m.size(), d + ox, x.size());
+  if ((rc = xchg_scatter(e, d, c.size(), d + om, m.size(), d + ox, x.size()))) return rc;
+  if (sp.total) {  // the granules are taken (ingest_share_commit)
+    u64* tot = (u64*)d;  // (the records are scattered: xchg_scatter synchronised)
+    HIP_OK(hipMemcpyAsync(tot, &sp.total, sizeof(u64), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_ing_commit, dim3(1), dim3(64), 0, e->stream, e->P, par, (const u64*)tot,
+                       (const u32*)nullptr);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(e->stream));
+    note_inbound_spill(e, sp.total);
+  }
+  return RBE_OK;
 }
 
 int rbe_kernel_name(const rbe_engine* e, int32_t kernel, char* buf, uint32_t cap) {
@@ -3372,6 +3402,12 @@ int rbe_spill_stats(rbe_engine* e, uint64_t* out) {
   return RBE_OK;
 }
 
+int rbe_inbound_spill_stats(rbe_engine* e, uint64_t* out) {
+  if (!e || !out) return RBE_E_INVALID;
+  for (int i = 0; i < 3; i++) out[i] = e->in_spill[i];
+  return RBE_OK;
+}
+
 int rbe_cold_tier_stats(rbe_engine* e, uint64_t* out) {
   if (!e || !out) return RBE_E_INVALID;
   HIP_OK(hipSetDevice(e->device));
@@ -3848,15 +3884,18 @@ static int wire_ingest_fast(rbe_engine* e, const void* data, uint64_t bytes,
     return RBE_E_HIP;
   const u64 o_sk = al(cm * 8), o_hb = o_sk + al(cm * 8), o_hs = o_hb + al(cm * 8);
   const u64 o_ix = o_hs + al(cm * 8), o_si = o_ix + al(cm * 4), o_top = o_si + al(cm * 4);
-  const u64 o_err = o_top + al((nbk + 1) * 8), o_tmp = o_err + 256;
+  const u64 o_sn = o_top + al((nbk + 1) * 8), o_st = o_sn + al(cm * 8);
+  const u64 o_err = o_st + al((nbk + 1) * 8), o_tmp = o_err + 256;
   if ((rc = e->ing_dev.reserve(o_tmp + al(tb)))) return rc;
   u8* b = e->ing_dev.p();
   u64 *key = (u64*)b, *skey = (u64*)(b + o_sk), *hb = (u64*)(b + o_hb), *hs = (u64*)(b + o_hs);
   u32 *idx = (u32*)(b + o_ix), *sidx = (u32*)(b + o_si);
   u64* top = (u64*)(b + o_top);
+  u64 *sn = (u64*)(b + o_sn), *stop = (u64*)(b + o_st);  // the runs' spill needs, their scan tops
   u32* err = (u32*)(b + o_err);     // [0] ingest checks (ING_*), [1] decode flags (WD_*)
   u32* dfl = err + 1;
   unsigned long long* ndrop = (unsigned long long*)(b + o_err + 8);
+  u64* ctl = (u64*)(b + o_err + 32);  // the share gate's words (IC_*)
   HIP_OK(hipMemsetAsync(b + o_err, 0, 16, e->stream));
   const unsigned g = (unsigned)nbk;
   hipLaunchKernelGGL(k_wire_frames_scan, dim3(1), dim3(256), 0, e->stream, wf.dfr, (u32)nf, cm,
@@ -3889,6 +3928,8 @@ static int wire_ingest_fast(rbe_engine* e, const void* data, uint64_t bytes,
   hipLaunchKernelGGL(k_scan_blocks, dim3(g), dim3(256), 0, e->stream, hs, cm, top);
   hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, e->stream, top, (u32)nbk);
   hipLaunchKernelGGL(k_scan_add, dim3(g), dim3(256), 0, e->stream, hs, cm, (const u64*)top);
+  // checking walk (the runs' spill needs), their scan, the share check on the
+  // device, the gated writing walk, the gated commit
   for (int wr = 0; wr < 2; wr++) {
     rc = dispatch_n(C.n, [&](auto NN) {
       constexpr int N = decltype(NN)::value;
@@ -3896,26 +3937,39 @@ static int wire_ingest_fast(rbe_engine* e, const void* data, uint64_t bytes,
         hipLaunchKernelGGL((k_ing_walk<N, true>), dim3(g), dim3(256), 0, e->stream, e->P, C, par,
                            e->round, (const u64*)skey, (const u32*)sidx, cm, (const rbe_message*)dm,
                            (const rbe_entry*)de, (const u64*)ec, (const u64*)ccn, (const u8*)dc,
-                           e->heap, (u64)C.heap_bytes, 0ull, (const u64*)hs, err, (const u32*)err);
+                           e->heap, (u64)C.heap_bytes, 0ull, (const u64*)hs, sn, (const u64*)ctl,
+                           (const u32*)err);
       else
         hipLaunchKernelGGL((k_ing_walk<N, false>), dim3(g), dim3(256), 0, e->stream, e->P, C, par,
                            e->round, (const u64*)skey, (const u32*)sidx, cm, (const rbe_message*)dm,
                            (const rbe_entry*)de, (const u64*)ec, (const u64*)ccn, (const u8*)dc,
-                           e->heap, (u64)C.heap_bytes, 0ull, (const u64*)hs, err, nullptr);
+                           e->heap, (u64)C.heap_bytes, 0ull, (const u64*)hs, sn, (const u64*)ctl,
+                           nullptr);
       HIP_OK(hipGetLastError());
       return RBE_OK;
     });
     if (rc) return rc;
+    if (wr) break;
+    hipLaunchKernelGGL(k_scan_blocks, dim3(g), dim3(256), 0, e->stream, sn, cm, stop);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, e->stream, stop, (u32)nbk);
+    hipLaunchKernelGGL(k_scan_add, dim3(g), dim3(256), 0, e->stream, sn, cm, (const u64*)stop);
+    hipLaunchKernelGGL(k_ing_share, dim3(1), dim3(64), 0, e->stream, e->P, C, par,
+                       (const u64*)(stop + nbk), ctl, err);
   }
-  u64 back[6];  // err | flags, drops, messages, entries, Cmd bytes, heap bytes
+  hipLaunchKernelGGL(k_ing_commit, dim3(1), dim3(64), 0, e->stream, e->P, par,
+                     (const u64*)(stop + nbk), (const u32*)err);
+  HIP_OK(hipGetLastError());
+  u64 back[7];  // err | flags, drops, messages, entries, Cmd bytes, heap bytes, spill granules
   HIP_OK(hipMemcpyAsync(back, err, 16, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipMemcpyAsync(back + 2, tot, 8, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipMemcpyAsync(back + 3, t1 + nbk, 8, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipMemcpyAsync(back + 4, t2 + nbk, 8, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipMemcpyAsync(back + 5, top + nbk, 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipMemcpyAsync(back + 6, ctl + IC_TOTAL, 8, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
   const u32 ferr = (u32)back[0], flags = (u32)(back[0] >> 32);
-  if (flags || back[5]) {  // nothing written: the exact path decides (and reports)
+  // nothing written: the exact path decides (and reports)
+  if (flags || back[5] || (ferr & ING_SHARE)) {
     *retry = true;
     return RBE_OK;
   }
@@ -3927,11 +3981,14 @@ static int wire_ingest_fast(rbe_engine* e, const void* data, uint64_t bytes,
   if (ferr & ING_INVALID) return RBE_E_INVALID;
   if (ferr & ING_NOMEM) return RBE_E_NOMEM;
   st->dropped = back[1];
+  note_inbound_spill(e, back[6]);
   return RBE_OK;
 }
 
 // Device ingest of inbound frames (rbe_ingest.h): decode, check, sort by inbox
-// list, check capacities, one read-back, reserve heap room, write the lists.
+// list, size what spills past maxm / ecap (rbe_ingest_spill.h) and check it
+// against this engine's share of the round spill heap, one read-back, reserve
+// heap room, write the lists, take the granules.
 // Without a payload heap, and once a call has measured the traffic, the whole
 // pipeline runs with one read-back at its end (wire_ingest_fast); the exact
 // path below reads counts back between its stages.
@@ -3969,14 +4026,17 @@ int rbe_wire_ingest(rbe_engine* e, const void* data, uint64_t bytes, rbe_wire_in
   // keys | sorted keys | heap bytes | sorted heap offsets | idx | sorted idx | tops | err | sort tmp
   const u64 o_sk = al(tm * 8), o_hb = o_sk + al(tm * 8), o_hs = o_hb + al(tm * 8);
   const u64 o_ix = o_hs + al(tm * 8), o_si = o_ix + al(tm * 4), o_top = o_si + al(tm * 4);
-  const u64 o_err = o_top + al((nbk + 1) * 8), o_tmp = o_err + 256;
+  const u64 o_sn = o_top + al((nbk + 1) * 8), o_st = o_sn + al(tm * 8);
+  const u64 o_err = o_st + al((nbk + 1) * 8), o_tmp = o_err + 256;
   if ((rc = e->ing_dev.reserve(o_tmp + al(tb)))) return rc;
   u8* b = e->ing_dev.p();
   u64 *key = (u64*)b, *skey = (u64*)(b + o_sk), *hb = (u64*)(b + o_hb), *hs = (u64*)(b + o_hs);
   u32 *idx = (u32*)(b + o_ix), *sidx = (u32*)(b + o_si);
   u64* top = (u64*)(b + o_top);
+  u64 *sn = (u64*)(b + o_sn), *stop = (u64*)(b + o_st);  // the runs' spill needs, their scan tops
   u32* err = (u32*)(b + o_err);
   unsigned long long* ndrop = (unsigned long long*)(b + o_err + 8);
+  u64* ctl = (u64*)(b + o_err + 32);  // the share gate's words (IC_*)
   HIP_OK(hipMemsetAsync(b + o_err, 0, 16, e->stream));
   const u32 par = (e->round - 1) & 1u;
   rc = dispatch_n(C.n, [&](auto NN) {
@@ -4003,25 +4063,42 @@ int rbe_wire_ingest(rbe_engine* e, const void* data, uint64_t bytes, rbe_wire_in
                            e->P, C, par, e->round, (const u64*)skey, (const u32*)sidx, tm,
                            (const rbe_message*)o.msgs, (const rbe_entry*)o.ents,
                            (const u64*)o.ent0, (const u64*)o.cmd0, (const u8*)o.cmd, e->heap,
-                           (u64)C.heap_bytes, base, (const u64*)hs, err);
+                           (u64)C.heap_bytes, base, (const u64*)hs, sn, (const u64*)ctl);
       else
         hipLaunchKernelGGL((k_ing_walk<N, false>), dim3((unsigned)nbk), dim3(256), 0, e->stream,
                            e->P, C, par, e->round, (const u64*)skey, (const u32*)sidx, tm,
                            (const rbe_message*)o.msgs, (const rbe_entry*)o.ents,
                            (const u64*)o.ent0, (const u64*)o.cmd0, (const u8*)o.cmd, e->heap,
-                           (u64)C.heap_bytes, base, (const u64*)hs, err);
+                           (u64)C.heap_bytes, base, (const u64*)hs, sn, (const u64*)ctl);
       HIP_OK(hipGetLastError());
       return RBE_OK;
     });
   };
+  // the runs' spill needs, their exclusive scan, and the batch's first granule
+  // (ingest_share_gate: share * rep_rank + SpillCtl::used[par]) with its verdict
   if ((rc = walk(false, 0))) return rc;
-  u64 back[3];  // err | drops, heap bytes
+  hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)nbk), dim3(256), 0, e->stream, sn, tm, stop);
+  hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, e->stream, stop, (u32)nbk);
+  hipLaunchKernelGGL(k_scan_add, dim3((unsigned)nbk), dim3(256), 0, e->stream, sn, tm,
+                     (const u64*)stop);
+  hipLaunchKernelGGL(k_ing_share, dim3(1), dim3(64), 0, e->stream, e->P, C, par,
+                     (const u64*)(stop + nbk), ctl, err);
+  HIP_OK(hipGetLastError());
+  u64 back[3 + IC_WORDS];  // err | drops, heap bytes, the gate's words
   HIP_OK(hipMemcpyAsync(back, b + o_err, 16, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipMemcpyAsync(back + 2, top + nbk, 8, hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipMemcpyAsync(back + 3, ctl, IC_WORDS * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_OK(hipStreamSynchronize(e->stream));
   const u32 ferr = (u32)back[0];
   if (ferr & ING_INVALID) return RBE_E_INVALID;
   if (ferr & ING_NOMEM) return RBE_E_NOMEM;
+  // the total need against share - used: refused whole, nothing written and
+  // SpillCtl untouched (no round ran out)
+  const u64 stot = back[3 + IC_TOTAL], sused = back[3 + IC_USED], share = spill_share(C);
+  if (stot > (sused < share ? share - sused : 0)) {
+    e->in_spill[2]++;
+    return RBE_E_NOMEM;
+  }
   st->dropped = back[1];
   const u64 need = back[2];
   st->heap_bytes = need;
@@ -4050,7 +4127,13 @@ int rbe_wire_ingest(rbe_engine* e, const void* data, uint64_t bytes, rbe_wire_in
                           e->stream));
   }
   if ((rc = walk(true, base))) return rc;
+  if (stot) {  // the granules are taken, after every reader of the base
+    hipLaunchKernelGGL(k_ing_commit, dim3(1), dim3(64), 0, e->stream, e->P, par,
+                       (const u64*)(stop + nbk), (const u32*)nullptr);
+    HIP_OK(hipGetLastError());
+  }
   HIP_OK(hipStreamSynchronize(e->stream));
+  note_inbound_spill(e, stot);
   return RBE_OK;
 }
 

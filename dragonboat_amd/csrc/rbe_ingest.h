@@ -18,11 +18,17 @@
 //                    payload-heap bytes its entries need
 //   radix sort       (list key, message index) pairs, stable: per list the
 //                    stream order is kept
-//   k_ing_walk<0>    lane per sender run: list capacities (maxm, ecap)
-//   host             one read-back: errors, heap bytes → HostHeap::room
+//   k_ing_walk<0>    lane per sender run: the granules of the round spill
+//                    heap its lists past maxm and entries past ecap need
+//   scan, k_ing_share  the needs' offsets, their total against this engine's share
+//   host             one read-back: errors, heap bytes → HostHeap::room, the share
 //   k_ing_walk<1>    lane per sender run: slots, entries, heap records, header
-// All integer/byte work; HBM bound, no MFMA.  The same functions run on the
-// host in the CPU test tier (tests/soa_cpu).
+//   k_ing_commit     the granules are taken
+// The walks are rbe_ingest_spill.h's (ingest_sender_spill); ingest_sender
+// below is the form that refuses what does not fit the planes, which the host
+// build keeps for comparison.  All integer/byte work; HBM bound, no MFMA.  The
+// same functions run on the host in the CPU test tier (tests/soa_cpu,
+// tests/ingest_cpu, tests/ingest_dev_cpu).
 #pragma once
 #include "rbe_xchg.h"
 
@@ -99,7 +105,7 @@ RBE_HD u64 ingest_check(const Params& C, u64 heap_cap, const rbe_message& m, con
     return drop;
   }
   // (`spill`: the caller keeps entries past the arena in the round spill heap,
-  // rbe_ingest_spill.h; rbe_wire_ingest does not yet)
+  // rbe_ingest_spill.h, as rbe_wire_ingest does)
   if (!spill && (m.n_entries > 0xFFFFu || m.n_entries > C.ecap)) {
     *err |= ING_NOMEM;
     return drop;

@@ -26,8 +26,11 @@
 // peak after the write; the next round's reset (spill_clear_next) is what gives
 // the granules back, after that round has read them.
 //
-// All RBE_HD.  The CPU test tier runs them (tests/ingest_cpu); the HIP engine
-// does not call them yet (DESIGN.md §10 "Inbound spill").
+// All RBE_HD.  The CPU test tier runs them (tests/ingest_cpu), and so does the
+// HIP engine: the bodies of its kernels are the lane functions at the end of
+// this file (ingest_walk_lane, ingest_share_gate, ingest_share_commit), which
+// tests/ingest_dev_cpu runs as loops under the sanitizers (DESIGN.md §10
+// "Inbound spill").
 #pragma once
 #include "rbe_ingest.h"
 
@@ -211,6 +214,70 @@ RBE_HD u32 ingest_sender_spill(const Planes& P, const Params& C, u32 par, u32 ro
   P.cnt[par][sr] = row;
   P.gwake[sr / N] = GW_AWAKE;  // a message wakes the destination's group
   return 0;
+}
+
+// ------------------------------------------------ the device pipeline's lanes
+// rbe_wire_ingest (rbe_engine.hip) runs, after the sort and the heap-byte scan:
+//   ingest_walk_lane<N, false>   lane per sorted position: the run's granule
+//                                need at its start, 0 everywhere else
+//   exclusive scan of the needs  (k_scan_*), the total behind them
+//   ingest_share_gate            one lane: the share check, the batch's first
+//                                granule and its total into `ctl`
+//   ingest_walk_lane<N, true>    lane per sorted position: the run's lists
+//   ingest_share_commit          one lane: used += total, peak raised
+// The __global__ functions compute the lane index and call these, so the host
+// build runs the same index arithmetic.
+
+// the share check's refusal, ORed into the word the writing walk is gated on
+// (beside ING_INVALID / ING_NOMEM, rbe_ingest.h)
+enum : u32 { ING_SHARE = 4u };
+// what the gate leaves for the writing walk, the commit and the host
+enum : u32 { IC_BASE = 0, IC_TOTAL = 1, IC_USED = 2, IC_WORDS = 4 };
+
+// Sorted position p of nm: the granules its sender's run needs (need[p]; 0
+// when p starts no run), or with WRITE the run's lists, its spilled parts from
+// granule ctl[IC_BASE] + need[p] on (need scanned by then).  With WRITE a
+// non-zero gate word means a check before this one failed: nothing is written.
+template <int N, bool WRITE>
+RBE_HD void ingest_walk_lane(const Planes& P, const Params& C, u32 par, u32 round, const u64* skey,
+                             const u32* sidx, u64 p, u64 nm, const rbe_message* msgs,
+                             const rbe_entry* ents, const u64* ent0, const u64* cmd0, const u8* cmd,
+                             u8* heap, u64 heap_cap, u64 base, const u64* hs, u64* need,
+                             const u64* ctl, const u32* gate) {
+  if (p >= nm) return;
+  const bool start = ingest_run_start(C, skey, p);
+  if (!WRITE) need[p] = 0;
+  if (!start) return;
+  if (WRITE && gate && (gate[0] | gate[1])) return;
+  const u64 q = ingest_run_end(C, skey, p, nm);
+  if (WRITE)
+    ingest_sender_spill<N, true>(P, C, par, round, skey, sidx, p, q, msgs, ents, ent0, cmd0, cmd,
+                                 heap, heap_cap, base, hs, nullptr, ctl[IC_BASE] + need[p]);
+  else
+    ingest_sender_spill<N, false>(P, C, par, round, skey, sidx, p, q, msgs, ents, ent0, cmd0, cmd,
+                                  nullptr, heap_cap, 0, hs, &need[p], 0);
+}
+
+// The share check (one lane, before the writing walk): `total` granules
+// against what this engine's share of parity `par` has left.  ctl gets the
+// batch's first granule (share * rep_rank + used), the total and `used`; a
+// total past the free part ORs ING_SHARE into *gate.  Reads SpillCtl only.
+RBE_HD void ingest_share_gate(const Params& C, const SpillCtl* s, u32 par, u64 total, u64* ctl,
+                              u32* gate) {
+  const u64 share = spill_share(C), used = s->used[par];
+  const u64 avail = used < share ? share - used : 0;
+  ctl[IC_BASE] = (C.rep_world > 1 ? share * C.rep_rank : 0) + used;
+  ctl[IC_TOTAL] = total;
+  ctl[IC_USED] = used;
+  if (total > avail) *gate |= ING_SHARE;
+}
+
+// The commit (one lane, after the writing walk, which reads the base): the
+// granules are taken.  Plain stores; nothing else runs between two rounds.
+RBE_HD void ingest_share_commit(SpillCtl* s, u32 par, u64 total, const u32* gate) {
+  if (gate && (gate[0] | gate[1])) return;
+  s->used[par] += total;
+  if (total && s->peak[par] < s->used[par]) s->peak[par] = s->used[par];
 }
 
 }  // namespace rbe

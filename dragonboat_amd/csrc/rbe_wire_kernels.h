@@ -16,7 +16,7 @@
 #pragma once
 
 #include "rbe_wire.h"
-#include "rbe_ingest.h"
+#include "rbe_ingest_spill.h"
 
 namespace rbe {
 
@@ -1033,7 +1033,8 @@ __global__ __launch_bounds__(256) void k_ing_key(Params C, u64 heap_cap, rbe_mes
     ingest_ids<N>(C, ids, m);
     msgs[j] = m;
   }
-  const u64 k = ingest_check<N>(C, heap_cap, msgs[j], ents + ent0[j], &e, &h);
+  // (spill: a message's entries past ecap go to the round spill heap, k_ing_walk)
+  const u64 k = ingest_check<N>(C, heap_cap, msgs[j], ents + ent0[j], &e, &h, true);
   key[j] = k;
   idx[j] = (u32)j;
   hb[j] = h;
@@ -1047,22 +1048,32 @@ __global__ __launch_bounds__(256) void k_ing_gather(const u32* sidx, const u64* 
   if (p < nm) hs[p] = hb[sidx[p]];
 }
 
+// lane per sorted position (rbe_ingest_spill.h ingest_walk_lane): WRITE =
+// false leaves each sender run's granule need in need[] (scanned next), WRITE =
+// true writes the runs' lists, the spilled parts from ctl[IC_BASE] + need[p];
+// with `gate` (the no-read-back ingest) nothing at all when the checking
+// passes, the decode or the share check found anything (all-or-nothing)
 template <int N, bool WRITE>
 __global__ __launch_bounds__(256) void k_ing_walk(Planes P, Params C, u32 par, u32 round,
                                                   const u64* skey, const u32* sidx, u64 nm,
                                                   const rbe_message* msgs, const rbe_entry* ents,
                                                   const u64* ent0, const u64* cmd0, const u8* cmd,
                                                   u8* heap, u64 heap_cap, u64 base, const u64* hs,
-                                                  u32* err, const u32* gate = nullptr) {
+                                                  u64* need, const u64* ctl,
+                                                  const u32* gate = nullptr) {
   const u64 p = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (p >= nm || !ingest_run_start(C, skey, p)) return;
-  // the writing walk of the no-read-back ingest: nothing at all when the
-  // checking walk or the decode found anything (all-or-nothing)
-  if (WRITE && gate && (gate[0] | gate[1])) return;
-  const u64 q = ingest_run_end(C, skey, p, nm);
-  const u32 e = ingest_sender<N, WRITE>(P, C, par, round, skey, sidx, p, q, msgs, ents, ent0, cmd0,
-                                        cmd, heap, heap_cap, base, hs);
-  if (e) atomicOr(err, e);
+  ingest_walk_lane<N, WRITE>(P, C, par, round, skey, sidx, p, nm, msgs, ents, ent0, cmd0, cmd, heap,
+                             heap_cap, base, hs, need, ctl, gate);
+}
+
+// one lane: the scanned total of the needs against this engine's share of the
+// round spill heap (ingest_share_gate)
+__global__ void k_ing_share(Planes P, Params C, u32 par, const u64* total, u64* ctl, u32* gate) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) ingest_share_gate(C, P.sctl, par, *total, ctl, gate);
+}
+// one lane, after the writing walk: the granules are taken (ingest_share_commit)
+__global__ void k_ing_commit(Planes P, u32 par, const u64* total, const u32* gate) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) ingest_share_commit(P.sctl, par, *total, gate);
 }
 
 }  // namespace rbe

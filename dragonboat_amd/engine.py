@@ -227,7 +227,7 @@ EXPORTS = ["rbe_create", "rbe_destroy", "rbe_abi_version", "rbe_abi_sizes", "rbe
            "rbe_round", "rbe_run_timed", "rbe_prepare_run", "rbe_push_proposals", "rbe_push_read_index",
            "rbe_get_updates", "rbe_get_messages", "rbe_get_ready_to_reads", "rbe_get_entries",
            "rbe_get_views", "rbe_get_counters", "rbe_reset_counters", "rbe_fault_summary",
-           "rbe_spill_stats", "rbe_cold_tier_stats",
+           "rbe_spill_stats", "rbe_cold_tier_stats", "rbe_inbound_spill_stats",
            "rbe_footprint", "rbe_profile_rounds", "rbe_get_kernel_counters", "rbe_kernel_name",
            "rbe_xchg_record_bytes", "rbe_xchg_pack", "rbe_xchg_unpack", "rbe_get_outbox",
            "rbe_push_messages", "rbe_snapshot_bytes", "rbe_export_bytes", "rbe_export_groups", "rbe_export_groups_ex", "rbe_import_groups",
@@ -332,6 +332,7 @@ def load_library(path: Optional[str] = None):
         "rbe_fault_summary": (i32, [vp, P(u64), P(u32)]),
         "rbe_spill_stats": (i32, [vp, P(u64)]),
         "rbe_cold_tier_stats": (i32, [vp, P(u64)]),
+        "rbe_inbound_spill_stats": (i32, [vp, P(u64)]),
         "rbe_footprint": (i32, [P(RbeConfig), P(u64)]),
         "rbe_profile_rounds": (i32, [vp, u32, P(C.c_float)]),
         "rbe_get_kernel_counters": (i32, [vp, C.c_int32, P(u64)]),
@@ -1182,6 +1183,19 @@ class Engine(NodeInputs):
         out = (C.c_uint64 * 4)()
         _check(self.lib.rbe_cold_tier_stats(self.h, out), "rbe_cold_tier_stats")
         return dict(host_pages_used=out[0], host_pages=out[1], demoted=out[2], passes=out[3])
+
+    def inbound_spill_stats(self) -> Dict[str, int]:
+        """What the inbound batches (wire_ingest, push_messages) kept in the
+        round spill heap (rbe_inbound_spill_stats): bytes taken so far, batches
+        that spilled, batches refused because this engine's share was short."""
+        out = (C.c_uint64 * 3)()
+        _check(self.lib.rbe_inbound_spill_stats(self.h, out), "rbe_inbound_spill_stats")
+        return dict(bytes=out[0], batches=out[1], refused=out[2])
+
+    @property
+    def inbound_spill_bytes(self) -> int:
+        """Bytes of the round spill heap the inbound batches have taken so far."""
+        return self.inbound_spill_stats()["bytes"]
 
     def fault_summary(self):
         n = C.c_uint64()

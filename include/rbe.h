@@ -667,9 +667,15 @@ int rbe_wire_decode(rbe_engine* e, const void* data, uint64_t bytes, rbe_message
  * whose cluster id is its ClusterId (cid_base + g * cid_stride); a response
  * from a node that is not a member is dropped (Peer.Handle, peer.go:186-198);
  * a message for a replica not stepped here, a local message type or a bad
- * entry is RBE_E_INVALID, a list over cfg.maxm messages, a sender over
- * cfg.ecap entries or a full payload heap RBE_E_NOMEM, a bad frame
- * RBE_E_CORRUPT — checked whole before anything is delivered.  All frames of
+ * entry is RBE_E_INVALID, a bad frame RBE_E_CORRUPT.  A list of more than
+ * cfg.maxm messages and a message whose entries run past the sender's
+ * cfg.ecap are taken as Peer.Handle takes them: they are kept in this engine's
+ * share of the round spill heap (cfg.spill_bytes / rep_world per round parity,
+ * after what the last round's own senders used), in the layout a local
+ * sender's step leaves there.  RBE_E_NOMEM means that this share is short for
+ * what the batch would spill (rbe_inbound_spill_stats out[2]; the exhaustion
+ * flags and the peak of rbe_spill_stats do not move), or that the payload heap
+ * is full.  All of it is checked whole before anything is delivered.  All frames of
  * one round come in one call (concatenated streams of several senders are
  * fine); lists it does not name are empty.  Replaces transport.go:318-350
  * handleRequest → node.handleReceivedMessages (node.go:1030-1067). */
@@ -845,6 +851,12 @@ int rbe_spill_stats(rbe_engine* e, uint64_t* out /* 5 */);
  * out[3] demotion passes that moved at least one page.  All zero without a
  * tier.  rbe_spill_stats' out[0] counts the page pool's (HBM) pages alone. */
 int rbe_cold_tier_stats(rbe_engine* e, uint64_t* out /* 4 */);
+/* What the inbound batches (rbe_wire_ingest, rbe_push_messages) kept in the
+ * round spill heap since rbe_create: out[0] bytes taken, cumulative (lists
+ * past cfg.maxm, entries past cfg.ecap), out[1] batches that spilled, out[2]
+ * batches refused with RBE_E_NOMEM because this engine's share was short.
+ * Host counters of this engine object; a checkpoint does not carry them. */
+int rbe_inbound_spill_stats(rbe_engine* e, uint64_t* out /* 3 */);
 
 /* Replica-per-GPU mode (cfg.rep_world > 1).  The engine steps
  * only its own replicas; between rounds the host moves the messages of the
@@ -921,9 +933,12 @@ int rbe_set_iso_leaders(rbe_engine* e, const uint8_t* bits);
  *     One call per round carries every remote message of that round; lists it
  *     does not name are empty.  Entries with Cmds over 16 bytes or session
  *     fields are written to this engine's payload heap.  RBE_E_STATE when
- *     rep_world <= 1 (every sender is local), RBE_E_NOMEM when one (sender,
- *     destination) list exceeds cfg.maxm, one sender's entries cfg.ecap, or
- *     the heap has no room. */
+ *     rep_world <= 1 (every sender is local).  A (sender, destination) list of
+ *     more than cfg.maxm messages and entries past a sender's cfg.ecap are
+ *     kept in this engine's share of the round spill heap, as rbe_wire_ingest
+ *     keeps them; RBE_E_NOMEM when that share is short for what the batch
+ *     would spill (nothing is delivered, no exhaustion flag is raised) or the
+ *     payload heap has no room. */
 int rbe_get_outbox(rbe_engine* e, uint64_t replica, rbe_message* out, uint32_t cap,
                    uint32_t* n_out, rbe_entry* ents, uint32_t ent_cap, uint32_t* n_ents,
                    uint8_t* cmd, uint64_t cmd_cap, uint64_t* cmd_bytes);

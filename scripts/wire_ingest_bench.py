@@ -9,7 +9,13 @@ line with per-round times and volumes; run under rocprofv3 --stats for the
 kernel split.  The stream goes through pinned host buffers (a transport's
 socket buffers would be registered the same way), and frames hold
 --gpb groups each (the reference's transport batches up to 64 MB per
-connection, transport.go:511-538; one block walks each frame's top level)."""
+connection, transport.go:511-538; one block walks each frame's top level).
+
+--maxm / --ecap set the plane capacities (defaults 8 / 16: nothing spills).
+With an isolation schedule (--iso-period / --iso-len) longer than --ecap
+rounds every heal's catch-up Replicate is past the sender's arena, so the
+ingest keeps it in the round spill heap (rbe_ingest_spill.h); the line then
+also carries the spill peak in 16-B granules and rbe_inbound_spill_stats."""
 import argparse
 import ctypes as C
 import json
@@ -29,9 +35,15 @@ def main():
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--gpb", type=int, default=512, help="groups per frame")
+    ap.add_argument("--maxm", type=int, default=8, help="messages per inbox list")
+    ap.add_argument("--ecap", type=int, default=16, help="entries per sender arena row")
+    ap.add_argument("--iso-period", type=int, default=0, help="isolation schedule: period")
+    ap.add_argument("--iso-len", type=int, default=0, help="isolation schedule: rounds isolated")
     a = ap.parse_args()
     kw = dict(n_groups=a.groups, n_replicas=3, wl_enabled=True, wl_start_round=20,
-              maxm=8, ecap=16)
+              maxm=a.maxm, ecap=a.ecap)
+    if a.iso_period:
+        kw.update(iso_period=a.iso_period, iso_len=a.iso_len, iso_mod=1)
     engs = [Engine(device=0, trace=False, rep_world=2, rep_rank=r, **kw) for r in range(2)]
     hip = C.CDLL("libamdhip64.so")
     cap = 1 << 28
@@ -44,6 +56,11 @@ def main():
     vol = {"bytes": 0, "frames": 0, "messages": 0, "entries": 0}
 
     def hop(timed):
+        if a.iso_period:  # an epoch round: every engine gets the ORed leader bits
+            iso = [e.iso_leaders() for e in engs]
+            if iso[0] is not None:
+                for e in engs:
+                    e.set_iso_leaders(iso[0] | iso[1])
         for e in engs:
             t0 = time.perf_counter()
             e.step()
@@ -85,7 +102,18 @@ def main():
     R = a.rounds
     faults = [e.fault_summary()[0] for e in engs]
     c = [e.counters() for e in engs]
+    spill = {}
+    if (a.maxm, a.ecap, a.iso_period) != (8, 16, 0):
+        sp = [e.spill_stats() for e in engs]
+        ib = [e.inbound_spill_stats() for e in engs]
+        spill = {"maxm": a.maxm, "ecap": a.ecap, "iso": [a.iso_period, a.iso_len],
+                 "spill_peak_granules": [x["spill_peak_bytes"] // 16 for x in sp],
+                 "spill_oom": [x["oom"] for x in sp],
+                 "inbound_spill_granules": [x["bytes"] // 16 for x in ib],
+                 "inbound_spill_batches": [x["batches"] for x in ib],
+                 "inbound_refused": [x["refused"] for x in ib]}
     print(json.dumps({
+        **spill,
         "groups": a.groups, "replicas": 3, "engines": 2, "rounds": R, "groups_per_frame": a.gpb,
         "ms_per_round": {k: v * 1e3 / R for k, v in t.items()},
         "per_round": {k: v / R for k, v in vol.items()},
