@@ -98,15 +98,17 @@ RBE_HD u32 ce_padded(u32 len) { return (len + 15u) & ~15u; }
 // ones still staged for the next step, e.g. those of an rbe_launch), and a
 // record a lap below it has been overwritten (rbe_step.h heap_lapped's rule
 // with that head).
-RBE_HD u32 collect_entry(const Planes& P, const Params& C, const u8* heap, u64 heap_head, u64 r,
-                         u64 idx, CeEnt* out) {
+//
+// collect_ent_record is the Ent → record half, shared with the batched outbox
+// (rbe_outbox.h), whose entries come from a sender's arena row or the round
+// spill heap and carry the Index their message gives them.
+RBE_HD u32 collect_ent_record(const Params& C, const u8* heap, u64 heap_head, const Ent& x, u64 idx,
+                              CeEnt* out) {
   CeEnt o;
   o.e = rbe_entry{};
   o.src = kCeInline;
   o.plen = 0;
   *out = o;
-  Ent x;
-  if (!log_ent_at(P, C, r, P.core[r].last_index, idx, &x)) return CE_MISSING;
   o.e.index = idx;
   o.e.term = x.term;
   o.e.type = ent_type(x.type);
@@ -140,6 +142,19 @@ RBE_HD u32 collect_entry(const Planes& P, const Params& C, const u8* heap, u64 h
   }
   *out = o;
   return 0;
+}
+RBE_HD u32 collect_entry(const Planes& P, const Params& C, const u8* heap, u64 heap_head, u64 r,
+                         u64 idx, CeEnt* out) {
+  Ent x;
+  if (!log_ent_at(P, C, r, P.core[r].last_index, idx, &x)) {
+    CeEnt o;
+    o.e = rbe_entry{};
+    o.src = kCeInline;
+    o.plen = 0;
+    *out = o;
+    return CE_MISSING;
+  }
+  return collect_ent_record(C, heap, heap_head, x, idx, out);
 }
 
 // 16-B word w of an entry's padded Cmd: from the record's cmd field (inline)

@@ -72,6 +72,33 @@ __global__ __launch_bounds__(kBlock) void k_ce_ranges(Planes P, Params C, CeSrc 
 // 32-B sector); else every lane writes its own record as nine 8-B stores.
 static constexpr unsigned kCeGrid = 1024;
 static_assert(sizeof(rbe_entry) == 72, "k_ce_entries stores a record as nine 8-B words");
+// One trip's records of a block into the record array: lane t holds record
+// base + t (zero past the end).  STAGE: through s_rec as 16-B stores of the
+// contiguous run; else nine 8-B stores per lane.  Every lane of the block calls it.
+template <bool STAGE>
+__device__ __forceinline__ void ce_store_records(uint4* s_rec, const rbe_entry& rec,
+                                                 rbe_entry* ents, u64 base, u64 ne) {
+  const u64 j = base + threadIdx.x;
+  const u64* w = (const u64*)&rec;
+  if (STAGE) {
+    u64* mine = (u64*)s_rec + 9u * threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < 9; q++) mine[q] = w[q];
+    __syncthreads();
+    // the run's bytes rounded up to 16: the records of lanes past the end are
+    // zero and the record array has room for a whole block
+    const u64 left = ne - base;
+    const u32 nv = left < kBlock ? (u32)left : (u32)kBlock;
+    const u32 words = (nv * (u32)sizeof(rbe_entry) + 15u) / 16u;
+    uint4* dst = (uint4*)(ents + base);
+    for (u32 q = threadIdx.x; q < words; q += kBlock) dst[q] = s_rec[q];
+    __syncthreads();  // before the next trip overwrites the stage
+  } else if (j < ne) {
+    u64* dst = (u64*)(ents + j);
+#pragma unroll
+    for (int q = 0; q < 9; q++) dst[q] = w[q];
+  }
+}
 template <bool STAGE>
 __global__ __launch_bounds__(kBlock) void k_ce_entries(Planes P, Params C, const u8* heap,
                                                        u64 heap_head, const u64* tot, const u64* rep,
@@ -94,25 +121,7 @@ __global__ __launch_bounds__(kBlock) void k_ce_entries(Planes P, Params C, const
       plen[j] = x.plen;
       src[j] = x.src;
     }
-    const u64* w = (const u64*)&x.e;
-    if (STAGE) {
-      u64* mine = (u64*)s_rec + 9u * threadIdx.x;
-#pragma unroll
-      for (int q = 0; q < 9; q++) mine[q] = w[q];
-      __syncthreads();
-      // the run's bytes rounded up to 16: the records of lanes past the end are
-      // zero and the record array has room for a whole block
-      const u64 left = ne - base;
-      const u32 nv = left < kBlock ? (u32)left : (u32)kBlock;
-      const u32 words = (nv * (u32)sizeof(rbe_entry) + 15u) / 16u;
-      uint4* dst = (uint4*)(ents + base);
-      for (u32 q = threadIdx.x; q < words; q += kBlock) dst[q] = s_rec[q];
-      __syncthreads();  // before the next trip overwrites the stage
-    } else if (j < ne) {
-      u64* dst = (u64*)(ents + j);
-#pragma unroll
-      for (int q = 0; q < 9; q++) dst[q] = w[q];
-    }
+    ce_store_records<STAGE>(s_rec, x.e, ents, base, ne);
   }
 }
 

@@ -236,6 +236,8 @@ static int launch_scan(hipStream_t st, const u32* bsum, u32 nb, u64* pre) {
 // ---- batched entries (rbe_collect_entries / rbe_collect_entry_ranges); the
 // kernels use block_excl_scan and launch_scan above
 #include "rbe_collect_kernels.h"
+// ---- batched outbox (rbe_collect_outbox): messages with entries and Cmds
+#include "rbe_outbox_kernels.h"
 // ---- self-contained checkpoints (rbe_export_groups_ex, the heap section of
 // rbe_import_groups); the kernels use block_excl_scan and launch_scan above
 #include "rbe_checkpoint_kernels.h"
@@ -817,6 +819,11 @@ struct rbe_engine {
   // whether k_ce_entries stages a block's records in LDS (RBE_COLLECT_STAGE=0:
   // every lane stores its own)
   bool ce_stage = true;
+  // rbe_collect_outbox (ob_collect): a set of its own, laid out as ce_collect's:
+  // scratch sized by the range (s1) and by the messages and entries (s2), the
+  // device lists (meta) and Cmd bytes, and the pinned host copy
+  Scratch<DevMem> ob_s1, ob_s2, ob_meta, ob_cmd;
+  Scratch<PinnedMem> ob_host;
   // rbe_export_groups_ex and the heap section of rbe_import_groups (ck_export,
   // ck_import_heap): scratch sized by the replicas (s), the flat page list, the
   // gathered log section, the reference pairs with their sort and scan scratch,
@@ -3384,6 +3391,138 @@ int rbe_collect_entry_ranges(rbe_engine* e, uint64_t n, const uint64_t* replica,
   }
   CeSrc s{0, n, e->round, 0, nullptr, nullptr, nullptr};
   const int rc = ce_collect(e, s, replica, lo, hi, !(flags & RBE_ENTRIES_NO_CMDS), 2u, out);
+  if (rc) memset(out, 0, sizeof(*out));
+  return rc;
+}
+
+// rbe_collect_outbox: the messages of the senders of `a`, their entries and,
+// with `cmds`, the Cmd bytes, into the outbox's pinned buffer.  Whatever is
+// listed, a call is at most 12 kernel launches and a memset, 7 copies down
+// (the three totals, the Cmd total, the lists, the Cmd bytes, the error word
+// with each of the 3 waits) and 3 stream synchronisations (6 launches, 4 copies
+// and 2 waits without Cmds); when heap records are still staged for the next
+// step, two more copies at most and one more wait bring them to the device
+// first.
+static int ob_collect(rbe_engine* e, const ObArgs& a, bool cmds, rbe_outbox_list* out) {
+  HIP_OK(hipSetDevice(e->device));
+  auto al = [](u64 x) { return (x + 255) & ~255ull; };
+  const u32 nb = grid_for(a.count);
+  // scratch 1: error word | block sums (triples) | block prefixes (+ totals)
+  const u64 o_bs = 256, o_pre = o_bs + al(3ull * nb * sizeof(u32));
+  int rc = e->ob_s1.reserve(o_pre + al(scan_words(3, nb) * sizeof(u64)));
+  if (rc) return rc;
+  u32* err = (u32*)e->ob_s1.p();
+  u32* bsum = (u32*)(e->ob_s1.p() + o_bs);
+  u64* pre = (u64*)(e->ob_s1.p() + o_pre);
+  HIP_OK(hipMemsetAsync(err, 0, sizeof(u32), e->stream));
+  // records still staged for the next step (proposals pushed since the last
+  // one) go to the device heap first, as ce_collect uploads them; every record
+  // is judged by the host's head
+  if ((rc = heap_upload_staged(e))) return rc;
+  hipLaunchKernelGGL(k_ob_count, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C, a, bsum, err);
+  if ((rc = launch_scan<3>(e->stream, bsum, nb, pre))) return rc;
+  u64 tot[3];
+  u32 herr = 0;
+  HIP_OK(hipMemcpyAsync(tot, pre + 3ull * nb, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  if (herr) return collect_rc(herr);
+  const u64 n = tot[0], nm = tot[1], ne = tot[2];
+  const u32 nb2 = ne ? grid_for(ne) : 1u;
+  // the lists, laid out on the device as in the host copy: replicas | message
+  // offsets | messages | entry offsets | records (room for whole blocks of
+  // them) | Cmd offsets
+  const u64 m_moff = al(n * sizeof(u64)), m_msg = m_moff + al((n + 1) * sizeof(u64));
+  const u64 m_eoff = m_msg + al(nm * sizeof(rbe_message));
+  const u64 m_ent = m_eoff + al((nm + 1) * sizeof(u64));
+  const u64 m_coff = m_ent + al((u64)nb2 * kBlock * sizeof(rbe_entry));
+  const u64 m_end = m_coff + (cmds ? al((ne + 1) * sizeof(u64)) : 0);
+  if ((rc = e->ob_meta.reserve(m_end))) return rc;
+  // scratch 2: message sources | padded Cmd lengths | Cmd sources | block sums
+  // | block prefixes (+ the Cmd total)
+  const u64 o_len = al(nm * sizeof(ObSrc)), o_src = o_len + al(ne * sizeof(u32));
+  const u64 o_bs2 = o_src + al(ne * sizeof(u64)), o_pre2 = o_bs2 + al(2ull * nb2 * sizeof(u32));
+  if ((rc = e->ob_s2.reserve(o_pre2 + al(scan_words(2, nb2) * sizeof(u64))))) return rc;
+  u8* m = e->ob_meta.p();
+  ObSrc* msrc = (ObSrc*)e->ob_s2.p();
+  u32* plen = (u32*)(e->ob_s2.p() + o_len);
+  u64* src = (u64*)(e->ob_s2.p() + o_src);
+  u32* bsum2 = (u32*)(e->ob_s2.p() + o_bs2);
+  u64* pre2 = (u64*)(e->ob_s2.p() + o_pre2);
+  const ObCaps caps{n, nm, ne};
+  const ObOut oo{(u64*)m, (u64*)(m + m_moff), (rbe_message*)(m + m_msg), (u64*)(m + m_eoff), msrc};
+  hipLaunchKernelGGL(k_ob_msgs, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C, a,
+                     (const u64*)pre, oo, caps, err);
+  if (ne) {
+    const unsigned g = std::min(nb2, kCeGrid);
+    auto k = e->ce_stage ? k_ob_entries<true> : k_ob_entries<false>;
+    hipLaunchKernelGGL(k, dim3(g), dim3(kBlock), 0, e->stream, e->P, e->C, (const u8*)e->heap,
+                       (u64)e->hin.heap.head, (const u64*)(pre + 3ull * nb),
+                       (const u64*)(m + m_eoff), (const ObSrc*)msrc, (rbe_entry*)(m + m_ent), plen,
+                       src, caps, err);
+  }
+  u64 cmd_bytes = 0;
+  if (cmds) {
+    hipLaunchKernelGGL(k_ce_cmd_sum, dim3(nb2), dim3(kBlock), 0, e->stream, (const u32*)plen, ne,
+                       bsum2);
+    if ((rc = launch_scan<2>(e->stream, bsum2, nb2, pre2))) return rc;
+    hipLaunchKernelGGL(k_ce_cmd_off, dim3(nb2), dim3(kBlock), 0, e->stream, (const u32*)plen, ne,
+                       (const u64*)pre2, (u64*)(m + m_coff));
+    u64 units = 0;
+    HIP_OK(hipMemcpyAsync(&units, pre2 + 2ull * nb2, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    if (herr) return collect_rc(herr);
+    cmd_bytes = units * 16;
+    if ((rc = e->ob_cmd.reserve(cmd_bytes))) return rc;
+    CeCaps cc{n, ne, cmd_bytes};
+    if (cmd_bytes)
+      hipLaunchKernelGGL(k_ce_cmds, dim3(std::min(nb2, kCeCmdGrid)), dim3(kBlock), 0, e->stream,
+                         (const u8*)e->heap, ne, (const rbe_entry*)(m + m_ent), (const u64*)src,
+                         (const u64*)(m + m_coff), e->ob_cmd.p(), cc);
+  }
+  HIP_OK(hipGetLastError());
+  if ((rc = e->ob_host.reserve(m_end + al(cmd_bytes)))) return rc;
+  u8* h = e->ob_host.p();
+  HIP_OK(hipMemcpyAsync(h, m, m_end, hipMemcpyDeviceToHost, e->stream));
+  if (cmd_bytes)
+    HIP_OK(hipMemcpyAsync(h + m_end, e->ob_cmd.p(), cmd_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  if (herr) return collect_rc(herr);
+  out->n = n;
+  out->n_messages = nm;
+  out->n_entries = ne;
+  out->cmd_bytes = cmd_bytes;
+  out->replica = (const uint64_t*)h;
+  out->msg_off = (const uint64_t*)(h + m_moff);
+  out->messages = (const rbe_message*)(h + m_msg);
+  out->ent_off = (const uint64_t*)(h + m_eoff);
+  out->entries = (const rbe_entry*)(h + m_ent);
+  if (cmds) {
+    out->cmd_off = (const uint64_t*)(h + m_coff);
+    out->cmds = (const uint8_t*)(h + m_end);
+  }
+  return RBE_OK;
+}
+
+int rbe_collect_outbox(rbe_engine* e, uint64_t first, uint64_t count, uint32_t flags,
+                       int32_t dst_rank, rbe_outbox_list* out) {
+  if (!e || !out || count == 0 || first >= e->C.n_rep || count > e->C.n_rep - first ||
+      (flags & ~(RBE_COLLECT_REMOTE_MSGS | RBE_ENTRIES_NO_CMDS)) ||
+      !outbox_rank_ok(e->C, dst_rank))
+    return RBE_E_INVALID;
+  memset(out, 0, sizeof(*out));
+  out->first = first;
+  out->count = count;
+  static const uint64_t zero = 0;
+  if (e->round == 0) {  // no round has run: no outbox, empty lists
+    out->msg_off = out->ent_off = &zero;
+    if (!(flags & RBE_ENTRIES_NO_CMDS)) out->cmd_off = &zero;
+    return RBE_OK;
+  }
+  const ObArgs a{first, count, e->round, (flags & RBE_COLLECT_REMOTE_MSGS) ? 1u : 0u, dst_rank};
+  const int rc = ob_collect(e, a, !(flags & RBE_ENTRIES_NO_CMDS), out);
   if (rc) memset(out, 0, sizeof(*out));
   return rc;
 }

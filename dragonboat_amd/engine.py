@@ -212,6 +212,15 @@ class RbeEntryList(C.Structure):
                 ("cmds", C.POINTER(C.c_uint8))]
 
 
+class RbeOutboxList(C.Structure):
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("n", C.c_uint64),
+                ("n_messages", C.c_uint64), ("n_entries", C.c_uint64),
+                ("cmd_bytes", C.c_uint64), ("replica", C.POINTER(C.c_uint64)),
+                ("msg_off", C.POINTER(C.c_uint64)), ("messages", C.POINTER(RbeMessage)),
+                ("ent_off", C.POINTER(C.c_uint64)), ("entries", C.POINTER(RbeEntry)),
+                ("cmd_off", C.POINTER(C.c_uint64)), ("cmds", C.POINTER(C.c_uint8))]
+
+
 RBE_ENTRIES_TO_SAVE, RBE_ENTRIES_COMMITTED, RBE_ENTRIES_NO_CMDS = 1, 2, 0x100
 
 ENTRY_DTYPE = _np_dtype(RbeEntry)
@@ -239,7 +248,7 @@ EXPORTS = ["rbe_create", "rbe_destroy", "rbe_abi_version", "rbe_abi_sizes", "rbe
            "rbe_reject_config_change", "rbe_rate_limited", "rbe_restore_remotes",
            "rbe_snapshot_saved", "rbe_compact", "rbe_set_node_ids", "rbe_collect_step",
            "rbe_collect_step_begin", "rbe_collect_step_end", "rbe_collect_entries",
-           "rbe_collect_entry_ranges"]
+           "rbe_collect_entry_ranges", "rbe_collect_outbox"]
 KERNEL_SLOTS = 4
 
 _lib = None
@@ -307,6 +316,7 @@ def load_library(path: Optional[str] = None):
         "rbe_collect_entries": (i32, [vp, u64, u64, u32, P(RbeEntryList)]),
         "rbe_collect_entry_ranges": (i32, [vp, u64, P(u64), P(u64), P(u64), u32,
                                            P(RbeEntryList)]),
+        "rbe_collect_outbox": (i32, [vp, u64, u64, u32, C.c_int32, P(RbeOutboxList)]),
         "rbe_get_messages": (i32, [vp, u64, P(RbeMessage), u32, P(u32)]),
         "rbe_get_outbox": (i32, [vp, u64, P(RbeMessage), u32, P(u32), P(RbeEntry), u32, P(u32),
                                  vp, u64, P(u64)]),
@@ -537,6 +547,59 @@ def entry_ranges_args(replicas, los, his):
         raise ValueError("replicas, los and his differ in length")
     p = C.POINTER(C.c_uint64)
     return (len(r), r.ctypes.data_as(p), a.ctypes.data_as(p), b.ctypes.data_as(p)), (r, a, b)
+
+
+def outbox_list_call(fn, what, h, first, count, remote_only=False, dst_rank=-1, cmds=True,
+                     raw=False):
+    """rbe_collect_outbox (or the host build's twin): {sender replica:
+    (messages, entries, cmds)} of the senders listed, ascending, each value in
+    the shapes outbox_call returns (cmds None when cmds=False).  raw=True: the
+    lists themselves as numpy copies of the engine's buffers, a dict with
+    replica, msg_off, messages (MESSAGE_DTYPE), ent_off, entries (ENTRY_DTYPE),
+    cmd_off and cmds (uint8; None when the call returned none)."""
+    o = RbeOutboxList()
+    fl = (RBE_COLLECT_REMOTE_MSGS if remote_only else 0) | (0 if cmds else RBE_ENTRIES_NO_CMDS)
+    rc = fn(h, first, count, fl, dst_rank, C.byref(o))
+    if rc != 0:
+        e = EngineError(f"{what} failed with rc={rc}")
+        e.rc = rc
+        raise e
+
+    def arr(ptr, n, dtype):
+        if n == 0 or not ptr:
+            return np.zeros(0, dtype=dtype)
+        b = C.string_at(C.cast(ptr, C.c_void_p), n * np.dtype(dtype).itemsize)
+        return np.frombuffer(b, dtype=dtype).copy()
+
+    rep = arr(o.replica, o.n, np.uint64)
+    moff = arr(o.msg_off, o.n + 1, np.uint64)
+    msgs = arr(o.messages, o.n_messages, MESSAGE_DTYPE)
+    eoff = arr(o.ent_off, o.n_messages + 1, np.uint64)
+    ents = arr(o.entries, o.n_entries, ENTRY_DTYPE)
+    coff = arr(o.cmd_off, o.n_entries + 1, np.uint64) if o.cmd_off else None
+    blob = arr(o.cmds, o.cmd_bytes, np.uint8) if o.cmd_off else None
+    d = dict(replica=rep, msg_off=moff, messages=msgs, ent_off=eoff, entries=ents, cmd_off=coff,
+             cmds=blob)
+    return d if raw else outbox_list_split(d)
+
+
+def outbox_list_split(d):
+    """The raw lists of outbox_list_call as {sender: (messages, entries, cmds)}."""
+    rep, moff, eoff, coff = d["replica"], d["msg_off"], d["ent_off"], d["cmd_off"]
+    mraw, eraw = d["messages"].tobytes(), d["entries"].tobytes()
+    braw = d["cmds"].tobytes() if coff is not None else b""
+    ms, es = C.sizeof(RbeMessage), C.sizeof(RbeEntry)
+    res = {}
+    for i in range(len(rep)):
+        a, b = int(moff[i]), int(moff[i + 1])
+        ea, eb = int(eoff[a]), int(eoff[b])
+        m = [RbeMessage.from_buffer_copy(mraw, j * ms) for j in range(a, b)]
+        en = [RbeEntry.from_buffer_copy(eraw, j * es) for j in range(ea, eb)]
+        cm = None
+        if coff is not None:
+            cm = [braw[int(coff[j]):int(coff[j]) + en[j - ea].cmd_len] for j in range(ea, eb)]
+        res[int(rep[i])] = (m, en, cm)
+    return res
 
 
 def outbox_call(fn, h, replica, cap, ent_cap, cmd_cap):
@@ -1060,6 +1123,16 @@ class Engine(NodeInputs):
         entries of its Replicate and forwarded Propose messages and their
         whole Cmds (rbe_get_outbox): (messages, entries, cmds)."""
         return outbox_call(self.lib.rbe_get_outbox, self.h, replica, cap, ent_cap, cmd_cap)
+
+    def collect_outbox(self, first: int = 0, count: Optional[int] = None, remote_only=False,
+                       dst_rank: int = -1, cmds: bool = True, raw: bool = False):
+        """rbe_collect_outbox: the last round's messages of the senders in
+        replicas [first, first + count) with their entries and Cmds, gathered
+        on the device in one call: {sender: (messages, entries, cmds)} in the
+        shapes outbox() returns (outbox_list_call)."""
+        count = self.n_rep - first if count is None else count
+        return outbox_list_call(self.lib.rbe_collect_outbox, "rbe_collect_outbox", self.h, first,
+                                count, remote_only, dst_rank, cmds, raw)
 
     def push_messages(self, groups, msgs, ents, cmds=None):
         """Deliver one round's inbound batch from remote senders (rbe_push_messages);

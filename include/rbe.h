@@ -944,6 +944,59 @@ int rbe_get_outbox(rbe_engine* e, uint64_t replica, rbe_message* out, uint32_t c
                    uint8_t* cmd, uint64_t cmd_cap, uint64_t* cmd_bytes);
 int rbe_push_messages(rbe_engine* e, uint64_t n, const uint64_t* group, const rbe_message* msgs,
                       const rbe_entry* ents, const uint8_t* cmd);
+/* rbe_collect_outbox: the batched form of rbe_get_outbox.  The last round's
+ * messages of every sender in replicas [first, first + count), each WITH its
+ * entries and their Cmds (Update.Messages as a transport needs it), gathered
+ * on the device — a lane per sender for the messages, a lane per entry for the
+ * entries, 16 B per access for the Cmds — and copied into engine-owned pinned
+ * buffers with a fixed number of launches, copies and waits, whatever is listed.
+ *   Senders: the replicas of the range this engine steps that have at least
+ *     one message returned, ascending; a replica another rank steps is not
+ *     listed, and with rep_compact the indexes are the local ones.
+ *   Messages: per sender exactly those of rbe_get_outbox in its order —
+ *     destinations in ascending slot, per destination the Quiesce notice, the
+ *     Replicate messages, the rest; InstallSnapshot messages included; node
+ *     ids through the group's id row (rbe_set_node_ids).
+ *   Entries: message j owns entries[ent_off[j] .. ent_off[j + 1]): a
+ *     Replicate's with Index = LogIndex + 1 + i, a forwarded Propose's with
+ *     Index 0, none for any other type; every field as rbe_get_outbox fills it.
+ *   Cmds: laid out as rbe_entry_list's, NOT as rbe_get_outbox's — entry j's
+ *     Cmd is cmds[cmd_off[j] .. cmd_off[j] + entries[j].cmd_len), each cmd_off
+ *     a multiple of 16 and the bytes up to the next one zero (rbe_get_outbox
+ *     packs them back to back).  This is the one deliberate difference.
+ *   flags: RBE_COLLECT_REMOTE_MSGS keeps only the messages to replicas this
+ *     engine does not step; RBE_ENTRIES_NO_CMDS returns the records only
+ *     (cmd_off and cmds null; rbe_entry.cmd keeps the first 16 bytes).  Any
+ *     other bit is RBE_E_INVALID.
+ *   dst_rank: -1 for every destination the flags allow, or r >= 0 for only
+ *     the destinations rank r steps (one connection per remote NodeHost, as
+ *     rbe_wire_config.dst_rank).  It must be -1 when rep_world <= 1, and else
+ *     below rep_world and not this engine's own rank (RBE_E_INVALID).
+ * Lists past cfg.maxm and entries past a sender's cfg.ecap are read out of the
+ * round spill heap.  A heap record a later lap overwrote makes the whole call
+ * RBE_E_STATE with *out zeroed (records are judged by the host's heap head;
+ * those still staged for the next step are uploaded first, as
+ * rbe_collect_entries does).  Null e or out, count == 0 or a range past the
+ * engine's replicas is RBE_E_INVALID.  Before the first step the lists are
+ * empty (RBE_OK).  A call lists fewer than 2^32 messages and entries and less
+ * than 64 GiB of Cmd bytes.  The buffers are a set of their own: a list stays
+ * valid until the next rbe_collect_outbox, the next rbe_step / rbe_run, or
+ * rbe_destroy.  The call runs on the engine's stream and may come between
+ * rbe_collect_step_begin and _end. */
+typedef struct rbe_outbox_list {
+  uint64_t first, count;        /* the sender range asked for */
+  uint64_t n;                   /* senders listed: those with at least one message returned */
+  uint64_t n_messages, n_entries, cmd_bytes;
+  const uint64_t* replica;      /* n, ascending */
+  const uint64_t* msg_off;      /* n + 1: replica[i] owns messages[msg_off[i] .. msg_off[i+1]) */
+  const rbe_message* messages;  /* n_messages, in rbe_get_outbox's order within a sender */
+  const uint64_t* ent_off;      /* n_messages + 1: message j owns entries[ent_off[j] .. ent_off[j+1]) */
+  const rbe_entry* entries;     /* n_entries, every field as rbe_get_outbox fills it */
+  const uint64_t* cmd_off;      /* n_entries + 1, multiples of 16; null with RBE_ENTRIES_NO_CMDS */
+  const uint8_t* cmds;          /* cmd_bytes = cmd_off[n_entries]; pad bytes zero */
+} rbe_outbox_list;
+int rbe_collect_outbox(rbe_engine* e, uint64_t first, uint64_t count, uint32_t flags,
+                       int32_t dst_rank, rbe_outbox_list* out);
 
 /* Group-range snapshots: the complete protocol state of groups [first, first + count)
  * between two rounds (every replica's raft, remote, readIndex and log-window rows and
