@@ -238,6 +238,7 @@ static int launch_scan(hipStream_t st, const u32* bsum, u32 nb, u64* pre) {
 #include "rbe_collect_kernels.h"
 // ---- batched outbox (rbe_collect_outbox): messages with entries and Cmds
 #include "rbe_outbox_kernels.h"
+#include "rbe_dropped_kernels.h"
 // ---- self-contained checkpoints (rbe_export_groups_ex, the heap section of
 // rbe_import_groups); the kernels use block_excl_scan and launch_scan above
 #include "rbe_checkpoint_kernels.h"
@@ -824,6 +825,9 @@ struct rbe_engine {
   // device lists (meta) and Cmd bytes, and the pinned host copy
   Scratch<DevMem> ob_s1, ob_s2, ob_meta, ob_cmd;
   Scratch<PinnedMem> ob_host;
+  // rbe_collect_dropped (dr_collect): a set of its own, laid out the same way
+  Scratch<DevMem> dr_s1, dr_s2, dr_meta, dr_cmd;
+  Scratch<PinnedMem> dr_host;
   // rbe_export_groups_ex and the heap section of rbe_import_groups (ck_export,
   // ck_import_heap): scratch sized by the replicas (s), the flat page list, the
   // gathered log section, the reference pairs with their sort and scan scratch,
@@ -1053,6 +1057,7 @@ static int make_params(const rbe_config* cfg, Params* out) {
   // the payload heap holds host-pushed Cmds longer than 16 bytes
   C.heap_bytes = (cfg->heap_bytes + 255) & ~255ull;
   if (C.heap_bytes && !C.ext_inputs) return RBE_E_INVALID;
+  C.drop_lists = cfg->drop_lists ? 1u : 0u;
   if (spill_sizes(cfg, &C)) return RBE_E_INVALID;
   *out = C;
   return RBE_OK;
@@ -1534,6 +1539,8 @@ int rbe_import_groups(rbe_engine* e, const void* buf, uint64_t bytes, uint32_t f
   // imported groups start awake (group sleep, rbe_step.h); the next round
   // scans every group to rebuild the awake list and the sleeping totals
   HIP_OK(hipMemsetAsync(e->P.gwake + h.first, GW_AWAKE, h.count, e->stream));
+  // dropped entries are not part of a snapshot: the range lists none until it steps
+  if (e->P.dent) HIP_OK(hipMemsetAsync(e->P.dent + r0, 0, nr * sizeof(DentRow), e->stream));
   if (resume && has_heap) {
     // the records at their own positions; the host's view of the heap restarts
     // at the section's head with nothing staged and the live mark unknown
@@ -1574,7 +1581,7 @@ int rbe_footprint(const rbe_config* cfg, uint64_t* bytes) {
   Params C;
   int rc = make_params(cfg, &C);
   if (rc) return rc;
-  *bytes = bytes_of(C, nullptr) + C.heap_bytes;
+  *bytes = bytes_of(C, nullptr) + C.heap_bytes + (C.drop_lists ? C.n_rep * sizeof(DentRow) : 0);
   return RBE_OK;
 }
 
@@ -1664,6 +1671,9 @@ int rbe_create(const rbe_config* cfg, rbe_engine** out) {
   P.spill[0] = (u8*)ptrs[28];
   P.spill[1] = P.spill[0] + C.spill_units * 16;
   P.sctl = (SpillCtl*)ptrs[29];
+  // cfg.drop_lists: each replica's DroppedEntries list (rbe_spill.h dent_put_o)
+  P.dent = nullptr;
+  if (C.drop_lists && (rc = dev_fixed(e, &P.dent, C.n_rep * sizeof(DentRow), true))) return rc;
   if (C.host_pages) {
     // the cold log's host tier: pinned, device-mapped pages the kernels read
     // in place, and the demotion's move list (at most every HBM page in a pass)
@@ -3525,6 +3535,211 @@ int rbe_collect_outbox(rbe_engine* e, uint64_t first, uint64_t count, uint32_t f
   const int rc = ob_collect(e, a, !(flags & RBE_ENTRIES_NO_CMDS), out);
   if (rc) memset(out, 0, sizeof(*out));
   return rc;
+}
+
+// rbe_collect_dropped: the dropped entries and ReadIndex contexts of the
+// replicas of `a` and, with `cmds`, the entries' Cmd bytes, into the call's
+// pinned buffer.  Whatever is listed, a call is at most 13 kernel launches and
+// a memset, 7 copies down (the three totals, the Cmd total, the lists, the Cmd
+// bytes, the error word with each of the 3 waits) and 3 stream
+// synchronisations (7 launches, 4 copies and 2 waits without Cmds); when heap
+// records are still staged for the next step, two more copies at most and one
+// more wait bring them to the device first.
+static int dr_collect(rbe_engine* e, const DrArgs& a, bool cmds, rbe_dropped_list* out) {
+  HIP_OK(hipSetDevice(e->device));
+  auto al = [](u64 x) { return (x + 255) & ~255ull; };
+  const u32 nb = grid_for(a.count);
+  // scratch 1: error word | block sums (triples) | block prefixes (+ totals)
+  const u64 o_bs = 256, o_pre = o_bs + al(3ull * nb * sizeof(u32));
+  int rc = e->dr_s1.reserve(o_pre + al(scan_words(3, nb) * sizeof(u64)));
+  if (rc) return rc;
+  u32* err = (u32*)e->dr_s1.p();
+  u32* bsum = (u32*)(e->dr_s1.p() + o_bs);
+  u64* pre = (u64*)(e->dr_s1.p() + o_pre);
+  HIP_OK(hipMemsetAsync(err, 0, sizeof(u32), e->stream));
+  // records still staged for the next step go to the device heap first, as
+  // ce_collect uploads them; every record is judged by the host's head
+  if ((rc = heap_upload_staged(e))) return rc;
+  hipLaunchKernelGGL(k_dr_count, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C, a, bsum, err);
+  if ((rc = launch_scan<3>(e->stream, bsum, nb, pre))) return rc;
+  u64 tot[3];
+  u32 herr = 0;
+  HIP_OK(hipMemcpyAsync(tot, pre + 3ull * nb, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  if (herr) return collect_rc(herr);
+  const u64 n = tot[0], ne = tot[1], nri = tot[2];
+  const u32 nb2 = ne ? grid_for(ne) : 1u;
+  // the lists, laid out on the device as in the host copy: replicas | entry
+  // offsets | context offsets | contexts | records (room for whole blocks of
+  // them) | Cmd offsets
+  const u64 m_eoff = al(n * sizeof(u64)), m_roff = m_eoff + al((n + 1) * sizeof(u64));
+  const u64 m_ctx = m_roff + al((n + 1) * sizeof(u64));
+  const u64 m_ent = m_ctx + al(nri * sizeof(rbe_system_ctx));
+  const u64 m_coff = m_ent + al((u64)nb2 * kBlock * sizeof(rbe_entry));
+  const u64 m_end = m_coff + (cmds ? al((ne + 1) * sizeof(u64)) : 0);
+  if ((rc = e->dr_meta.reserve(m_end))) return rc;
+  // scratch 2: replica sources | padded Cmd lengths | Cmd sources | block sums
+  // | block prefixes (+ the Cmd total)
+  const u64 o_len = al(n * sizeof(DrSrc)), o_src = o_len + al(ne * sizeof(u32));
+  const u64 o_bs2 = o_src + al(ne * sizeof(u64)), o_pre2 = o_bs2 + al(2ull * nb2 * sizeof(u32));
+  if ((rc = e->dr_s2.reserve(o_pre2 + al(scan_words(2, nb2) * sizeof(u64))))) return rc;
+  u8* m = e->dr_meta.p();
+  DrSrc* dsrc = (DrSrc*)e->dr_s2.p();
+  u32* plen = (u32*)(e->dr_s2.p() + o_len);
+  u64* src = (u64*)(e->dr_s2.p() + o_src);
+  u32* bsum2 = (u32*)(e->dr_s2.p() + o_bs2);
+  u64* pre2 = (u64*)(e->dr_s2.p() + o_pre2);
+  const DrCaps caps{n, ne, nri};
+  const DrOut oo{(u64*)m, (u64*)(m + m_eoff), (u64*)(m + m_roff), dsrc};
+  hipLaunchKernelGGL(k_dr_write, dim3(nb), dim3(kBlock), 0, e->stream, e->P, e->C, a,
+                     (const u64*)pre, oo, caps, err);
+  if (ne) {
+    const unsigned g = std::min(nb2, kCeGrid);
+    auto k = e->ce_stage ? k_dr_entries<true> : k_dr_entries<false>;
+    hipLaunchKernelGGL(k, dim3(g), dim3(kBlock), 0, e->stream, e->P, e->C, (const u8*)e->heap,
+                       (u64)e->hin.heap.head, (const u64*)(pre + 3ull * nb),
+                       (const u64*)(m + m_eoff), (const DrSrc*)dsrc, (rbe_entry*)(m + m_ent), plen,
+                       src, caps, err);
+  }
+  if (nri)
+    hipLaunchKernelGGL(k_dr_ctx, dim3(std::min(grid_for(nri), kCeGrid)), dim3(kBlock), 0, e->stream,
+                       e->P, (const u64*)(pre + 3ull * nb), (const u64*)(m + m_roff),
+                       (const DrSrc*)dsrc, (rbe_system_ctx*)(m + m_ctx), caps);
+  u64 cmd_bytes = 0;
+  if (cmds) {
+    hipLaunchKernelGGL(k_ce_cmd_sum, dim3(nb2), dim3(kBlock), 0, e->stream, (const u32*)plen, ne,
+                       bsum2);
+    if ((rc = launch_scan<2>(e->stream, bsum2, nb2, pre2))) return rc;
+    hipLaunchKernelGGL(k_ce_cmd_off, dim3(nb2), dim3(kBlock), 0, e->stream, (const u32*)plen, ne,
+                       (const u64*)pre2, (u64*)(m + m_coff));
+    u64 units = 0;
+    HIP_OK(hipMemcpyAsync(&units, pre2 + 2ull * nb2, sizeof(u64), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    if (herr) return collect_rc(herr);
+    cmd_bytes = units * 16;
+    if ((rc = e->dr_cmd.reserve(cmd_bytes))) return rc;
+    CeCaps cc{n, ne, cmd_bytes};
+    if (cmd_bytes)
+      hipLaunchKernelGGL(k_ce_cmds, dim3(std::min(nb2, kCeCmdGrid)), dim3(kBlock), 0, e->stream,
+                         (const u8*)e->heap, ne, (const rbe_entry*)(m + m_ent), (const u64*)src,
+                         (const u64*)(m + m_coff), e->dr_cmd.p(), cc);
+  }
+  HIP_OK(hipGetLastError());
+  if ((rc = e->dr_host.reserve(m_end + al(cmd_bytes)))) return rc;
+  u8* h = e->dr_host.p();
+  HIP_OK(hipMemcpyAsync(h, m, m_end, hipMemcpyDeviceToHost, e->stream));
+  if (cmd_bytes)
+    HIP_OK(hipMemcpyAsync(h + m_end, e->dr_cmd.p(), cmd_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipMemcpyAsync(&herr, err, sizeof(u32), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  if (herr) return collect_rc(herr);
+  out->n = n;
+  out->n_entries = ne;
+  out->n_read_indexes = nri;
+  out->cmd_bytes = cmd_bytes;
+  out->replica = (const uint64_t*)h;
+  out->ent_off = (const uint64_t*)(h + m_eoff);
+  out->ri_off = (const uint64_t*)(h + m_roff);
+  out->read_indexes = (const rbe_system_ctx*)(h + m_ctx);
+  out->entries = (const rbe_entry*)(h + m_ent);
+  if (cmds) {
+    out->cmd_off = (const uint64_t*)(h + m_coff);
+    out->cmds = (const uint8_t*)(h + m_end);
+  }
+  return RBE_OK;
+}
+
+int rbe_collect_dropped(rbe_engine* e, uint64_t first, uint64_t count, uint32_t flags,
+                        rbe_dropped_list* out) {
+  if (!e || !out || count == 0 || first >= e->C.n_rep || count > e->C.n_rep - first ||
+      (flags & ~RBE_ENTRIES_NO_CMDS))
+    return RBE_E_INVALID;
+  if (!e->C.drop_lists) return RBE_E_STATE;
+  memset(out, 0, sizeof(*out));
+  out->first = first;
+  out->count = count;
+  static const uint64_t zero = 0;
+  if (e->round == 0) {  // no round has run: no Update, empty lists
+    out->ent_off = out->ri_off = &zero;
+    if (!(flags & RBE_ENTRIES_NO_CMDS)) out->cmd_off = &zero;
+    return RBE_OK;
+  }
+  const DrArgs a{first, count, e->round};
+  const int rc = dr_collect(e, a, !(flags & RBE_ENTRIES_NO_CMDS), out);
+  if (rc) memset(out, 0, sizeof(*out));
+  return rc;
+}
+
+// One replica's dropped lists with plain copies, as rbe_get_ready_to_reads
+// reads P.rtr: the Upd, the P.dent row and the P.dri list, then the blocks
+// they name in the round spill heap; heap records through read_heap.
+int rbe_get_dropped(rbe_engine* e, uint64_t replica, rbe_entry* ents, uint32_t ent_cap,
+                    uint32_t* n_ents, uint8_t* cmd, uint64_t cmd_cap, uint64_t* cmd_bytes,
+                    rbe_system_ctx* ctx, uint32_t ctx_cap, uint32_t* n_ctx) {
+  if (!e || !n_ents || !n_ctx || replica >= e->C.n_rep) return RBE_E_INVALID;
+  if (!e->C.drop_lists) return RBE_E_STATE;
+  HIP_OK(hipSetDevice(e->device));
+  *n_ents = *n_ctx = 0;
+  if (cmd_bytes) *cmd_bytes = 0;
+  if (e->round == 0 || !owns_replica(e->C, replica / e->C.n, (u32)(replica % e->C.n)))
+    return RBE_OK;
+  Upd u;
+  DentRow d;
+  std::vector<DropRI> ri(e->C.dri_cap);
+  HIP_OK(hipMemcpyAsync(&u, e->P.upd + replica, sizeof(u), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipMemcpyAsync(&d, e->P.dent + replica, sizeof(d), hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipMemcpyAsync(ri.data(), e->P.dri + replica * e->C.dri_cap, ri.size() * sizeof(DropRI),
+                        hipMemcpyDeviceToHost, e->stream));
+  HIP_OK(hipStreamSynchronize(e->stream));
+  if (u.round != e->round - 1 || !(u.flags & UF_RANGES)) return RBE_OK;
+  const u32 par = u.round & 1u;
+  const u64 units = e->C.spill_units;
+  const u32 nri = u.n_drop_ri;
+  // both blocks are checked before either copy is queued: no return leaves a
+  // copy pending into a local vector
+  const bool ri_x = nri > e->C.dri_cap, ent_x = u.n_drop_ent && d.round == u.round && d.n;
+  const u64 gr = ri_x ? ri[0].low : 0;
+  if (ri_x && (gr > units || nri > units - gr)) return RBE_E_STATE;
+  if (ent_x && (d.granule > units || d.n > d.cap || (u64)d.cap * 2 > units - d.granule))
+    return RBE_E_STATE;
+  if (ri_x) {  // the list moved to the round spill heap (rbe_spill.h dri_list)
+    ri.resize(nri);
+    HIP_OK(hipMemcpyAsync(ri.data(), e->P.spill[par] + gr * 16, nri * sizeof(DropRI),
+                          hipMemcpyDeviceToHost, e->stream));
+  }
+  std::vector<Ent> en;
+  if (ent_x) {
+    en.resize(d.n);
+    HIP_OK(hipMemcpyAsync(en.data(), e->P.spill[par] + (u64)d.granule * 16, d.n * sizeof(Ent),
+                          hipMemcpyDeviceToHost, e->stream));
+  }
+  HIP_OK(hipStreamSynchronize(e->stream));
+  for (u32 i = 0; i < nri && i < ctx_cap && ctx; i++) {
+    ctx[i].low = ri[i].low;
+    ctx[i].high = ri[i].high;
+  }
+  *n_ctx = nri;
+  auto rd = [e](u64 pos, u64 off, u64 len, u8* dst) { return read_heap(e, pos, off, len, dst); };
+  u64 nc = 0;
+  for (u32 i = 0; i < en.size(); i++) {
+    const Ent& x = en[i];
+    const bool room_c = cmd && nc + x.len <= cmd_cap;
+    rbe_entry tmp;
+    rbe_entry* o = (ents && i < ent_cap) ? &ents[i] : &tmp;
+    *o = rbe_entry{};
+    const int rc = entry_out(x, o, room_c ? cmd + nc : nullptr, rd);
+    if (rc) {
+      HIP_IGNORE(hipStreamSynchronize(e->stream));
+      return rc;
+    }
+    nc += x.len;
+  }
+  HIP_OK(hipStreamSynchronize(e->stream));  // heap reads
+  *n_ents = (u32)en.size();
+  if (cmd_bytes) *cmd_bytes = nc;
+  return RBE_OK;
 }
 
 int rbe_spill_stats(rbe_engine* e, uint64_t* out) {

@@ -711,6 +711,40 @@ RBE_COLD ColdRef cold_release_o(SpillRef s, ColdRef cr, u64 upto, u32 par) {
 RBE_COLD u64 spill_alloc_o(SpillRef s, u32 par, u64 bytes) {
   return spill_alloc(s.P, s.C, par, bytes);
 }
+// cfg.drop_lists: dropped entry `e` joins the list `row` names, in the round
+// spill heap of parity `par` (`first`: the step's first drop, so whatever the
+// row holds is stale).  The list grows as the step's other output lists do
+// (rbe_step.h out_list_put: twice the size, copy), from kDentFloor records.
+// False once, when the heap has no room: the row then says n = 0 and
+// kDentFailed, and the step's later drops are not kept.
+RBE_COLD u32 dent_put_o(SpillRef s, DentRow* row, u32 par, u32 round, u32 first, Ent e) {
+  DentRow d = *row;
+  if (first) {
+    d.granule = d.cap = d.n = 0;
+    d.round = round;
+  } else if (d.granule == kDentFailed) {
+    return 1u;
+  }
+  if (d.n >= d.cap) {
+    const u32 cap = d.n * 2u < kDentFloor ? kDentFloor : d.n * 2u;
+    const u64 g = spill_alloc(s.P, s.C, par, (u64)cap * sizeof(Ent));
+    if (g >= kDentFailed) {  // exhausted (~0), or past what a row can name
+      d.granule = kDentFailed;
+      d.cap = d.n = 0;
+      *row = d;
+      return 0u;
+    }
+    Ent* nb = spill_at<Ent>(s.P, par, g);
+    const Ent* ob = spill_at<const Ent>(s.P, par, d.granule);
+    for (u32 i = 0; i < d.n; i++) nb[i] = ob[i];
+    d.granule = (u32)g;
+    d.cap = cap;
+  }
+  spill_at<Ent>(s.P, par, d.granule)[d.n] = e;
+  d.n++;
+  *row = d;
+  return 1u;
+}
 RBE_COLD u32 pool_alloc_o(SpillRef s, u32 par) {
   return pool_alloc(s.P, s.C, par);
 }

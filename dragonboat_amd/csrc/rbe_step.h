@@ -1215,9 +1215,18 @@ struct Lane {
     add_dropped_ri(low, high);
     events |= EV_READ_INDEX_DROPPED;
   }
+  // cfg.drop_lists: a copy of dropped entry `e` joins the step's list in the
+  // round spill heap (called before n_drop_ent counts it).  Drops are rare, so
+  // the list's block and counts live in the replica's P.dent row, re-read on
+  // every append, not in LaneX.  No room: F_NOMEM, and the row says n = 0.
+  RBE_HD void keep_dropped(const Ent& e) {
+    if (!dent_put_o(spill_ref(P, C), &P.dent[r], par, round, n_drop_ent == 0 ? 1u : 0u, e))
+      set_fault(F_NOMEM);
+  }
   RBE_HD void report_dropped_proposal(const Ent* e, u32 cnt) {  // raft.go:1987-1997
     if (cnt) events |= EV_PROPOSAL_DROPPED;
     for (u32 i = 0; i < cnt; i++) {
+      if (C.drop_lists) keep_dropped(e[i]);
       n_drop_ent++;
       if (TRACE) {
         drop_hash = hfold(drop_hash, 0);
@@ -1736,6 +1745,7 @@ struct Lane {
         if (flags & HF_PENDING_CC) {
           // reportDroppedConfigChange (raft.go:1983-1985): the entry joins
           // DroppedEntries and an empty application entry takes its place
+          if (C.drop_lists) keep_dropped(e);
           n_drop_ent++;
           if (TRACE) {
             drop_hash = hfold(drop_hash, 0);
@@ -3530,6 +3540,7 @@ RBE_HD void launch_replica(const Planes& P, const Params& C, u64 r, bool join = 
   u.round = ~0u;
   u.cc_acc = 0;
   P.upd[r] = u;
+  if (C.drop_lists) P.dent[r] = DentRow{};
 }
 
 // Restart of replica r from persisted state (rbe_launch): Peer.Launch over an
@@ -3560,6 +3571,7 @@ RBE_HD void relaunch_replica(const Planes& P, const Params& C, u64 r, u64 term, 
   // the old incarnation's cold log and readIndex queue pages go back to the pool
   const u32 par = ppar ^ 1u;
   spill_replica_release(P, C, r, par);
+  if (C.drop_lists) P.dent[r] = DentRow{};  // (its dropped entries list nothing until it steps)
   u32 sfault = 0;
   if (C.snapshot_entries) {
     SnapSt& sp = P.snp[r];

@@ -273,6 +273,17 @@ struct RTR {  // ReadyToRead, raftpb/raft.go:52-56
 struct DropRI {  // SystemCtx
   u64 low, high;
 };
+// The DroppedEntries of a replica's last general step (cfg.drop_lists): `n`
+// Ent records in append order at `granule` of the round spill heap of parity
+// round & 1, in a block of `cap` records.  Written by the step that drops (the
+// one that raises Upd::n_drop_ent); a row of another round than the replica's
+// Upd is stale.  A list the heap had no room for leaves n = 0 and kDentFailed
+// (the step has raised F_NOMEM).
+struct alignas(16) DentRow {
+  u32 granule, cap, n, round;
+};
+static constexpr u32 kDentFailed = ~0u;
+static constexpr u32 kDentFloor = 4;  // records of a list's first block
 
 // Host-pushed input of one replica, consumed by the next step: the node-side
 // events of handleEvents (node.go:1030-1067) that are not network messages
@@ -354,6 +365,8 @@ struct Params {
   // replica mode with compacted planes (rbe_xchg.h rep_compact_setup): local
   // group l is global group (l / n) * rep_world + res[l % n]
   u32 rep_compact;
+  u32 drop_lists;     // cfg.drop_lists: the general step keeps its DroppedEntries (Planes::dent);
+                      // (in the padding before n_groups_glob: sizeof(Params) is unchanged)
   u64 n_groups_glob;  // global group count (= n_groups without compaction)
   u8 res[8];          // the n residues g % rep_world of the groups this rank touches, ascending
   u64 rl_max;         // config.MaxInMemLogSize (server.NewRateLimiter); 0 = limiter off
@@ -519,6 +532,7 @@ struct Planes {
   ColdRef* cold;      // [n_rep] each replica's cold log
   u8* spill[2];       // [spill_units * 16] round spill heap, by round parity
   SpillCtl* sctl;     // [1]
+  DentRow* dent;      // [n_rep] each replica's DroppedEntries list (Params::drop_lists, else null)
 };
 
 // Store audit of the fast step (scripts/store_audit.py): a host

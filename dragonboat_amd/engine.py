@@ -14,7 +14,7 @@ import numpy as np
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libdragonboat_amd.so")
-RBE_ABI_VERSION = 10
+RBE_ABI_VERSION = 11
 
 COUNTER_NAMES = ["steps", "committed", "msg_in", "msg_out", "ent_in", "ent_out",
                  "reads_confirmed", "proposals", "reads", "quiesced_ticks", "active_ticks",
@@ -49,7 +49,8 @@ class RbeConfig(C.Structure):
                 ("rep_compact", C.c_uint32), ("n_voters", C.c_uint32),
                 ("max_inmem_log_size", C.c_uint64), ("observer_slots", C.c_uint32),
                 ("witness_slots", C.c_uint32), ("pool_bytes", C.c_uint64),
-                ("spill_bytes", C.c_uint64), ("host_pool_bytes", C.c_uint64)]
+                ("spill_bytes", C.c_uint64), ("host_pool_bytes", C.c_uint64),
+                ("drop_lists", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class RbeReplicaView(C.Structure):
@@ -221,12 +222,26 @@ class RbeOutboxList(C.Structure):
                 ("cmd_off", C.POINTER(C.c_uint64)), ("cmds", C.POINTER(C.c_uint8))]
 
 
+class RbeSystemCtx(C.Structure):  # pb.SystemCtx
+    _fields_ = [("low", C.c_uint64), ("high", C.c_uint64)]
+
+
+class RbeDroppedList(C.Structure):
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("n", C.c_uint64),
+                ("n_entries", C.c_uint64), ("n_read_indexes", C.c_uint64),
+                ("cmd_bytes", C.c_uint64), ("replica", C.POINTER(C.c_uint64)),
+                ("ent_off", C.POINTER(C.c_uint64)), ("entries", C.POINTER(RbeEntry)),
+                ("cmd_off", C.POINTER(C.c_uint64)), ("cmds", C.POINTER(C.c_uint8)),
+                ("ri_off", C.POINTER(C.c_uint64)), ("read_indexes", C.POINTER(RbeSystemCtx))]
+
+
 RBE_ENTRIES_TO_SAVE, RBE_ENTRIES_COMMITTED, RBE_ENTRIES_NO_CMDS = 1, 2, 0x100
 
 ENTRY_DTYPE = _np_dtype(RbeEntry)
 MESSAGE_DTYPE = _np_dtype(RbeMessage)
 UPDATE_DTYPE = _np_dtype(RbeUpdate)
 RTR_DTYPE = _np_dtype(RbeReadyToRead)
+CTX_DTYPE = _np_dtype(RbeSystemCtx)
 
 
 # exported symbols of include/rbe.h (checked by tests/test_capi.py)
@@ -248,7 +263,8 @@ EXPORTS = ["rbe_create", "rbe_destroy", "rbe_abi_version", "rbe_abi_sizes", "rbe
            "rbe_reject_config_change", "rbe_rate_limited", "rbe_restore_remotes",
            "rbe_snapshot_saved", "rbe_compact", "rbe_set_node_ids", "rbe_collect_step",
            "rbe_collect_step_begin", "rbe_collect_step_end", "rbe_collect_entries",
-           "rbe_collect_entry_ranges", "rbe_collect_outbox"]
+           "rbe_collect_entry_ranges", "rbe_collect_outbox", "rbe_collect_dropped",
+           "rbe_get_dropped"]
 KERNEL_SLOTS = 4
 
 _lib = None
@@ -317,6 +333,9 @@ def load_library(path: Optional[str] = None):
         "rbe_collect_entry_ranges": (i32, [vp, u64, P(u64), P(u64), P(u64), u32,
                                            P(RbeEntryList)]),
         "rbe_collect_outbox": (i32, [vp, u64, u64, u32, C.c_int32, P(RbeOutboxList)]),
+        "rbe_collect_dropped": (i32, [vp, u64, u64, u32, P(RbeDroppedList)]),
+        "rbe_get_dropped": (i32, [vp, u64, P(RbeEntry), u32, P(u32), vp, u64, P(u64),
+                                  P(RbeSystemCtx), u32, P(u32)]),
         "rbe_get_messages": (i32, [vp, u64, P(RbeMessage), u32, P(u32)]),
         "rbe_get_outbox": (i32, [vp, u64, P(RbeMessage), u32, P(u32), P(RbeEntry), u32, P(u32),
                                  vp, u64, P(u64)]),
@@ -395,7 +414,7 @@ def make_config(n_groups: int, n_replicas: int = 3, device: int = 0, election_rt
                 cc_mod: int = 1, rep_compact: bool = False,
                 max_inmem_log_size: int = 0, n_voters: int = 0, observer_slots: int = 0,
                 witness_slots: int = 0, pool_bytes: int = 0, spill_bytes: int = 0,
-                host_pool_bytes: int = 0) -> RbeConfig:
+                host_pool_bytes: int = 0, drop_lists: bool = False) -> RbeConfig:
     return RbeConfig(abi_version=RBE_ABI_VERSION, device=device, n_groups=n_groups,
                      n_replicas=n_replicas, election_rtt=election_rtt,
                      heartbeat_rtt=heartbeat_rtt, check_quorum=int(check_quorum),
@@ -414,7 +433,8 @@ def make_config(n_groups: int, n_replicas: int = 3, device: int = 0, election_rt
                      rep_compact=int(rep_compact), max_inmem_log_size=max_inmem_log_size,
                      n_voters=n_voters, observer_slots=observer_slots,
                      witness_slots=witness_slots, pool_bytes=pool_bytes,
-                     spill_bytes=spill_bytes, host_pool_bytes=host_pool_bytes)
+                     spill_bytes=spill_bytes, host_pool_bytes=host_pool_bytes,
+                     drop_lists=int(drop_lists))
 
 
 class InputError(EngineError):
@@ -619,6 +639,74 @@ def outbox_call(fn, h, replica, cap, ent_cap, cmd_cap):
         cmds.append(raw[off:off + e.cmd_len])
         off += e.cmd_len
     return [arr[i] for i in range(n.value)], es, cmds
+
+
+def dropped_list_call(fn, what, h, first, count, cmds=True, raw=False):
+    """rbe_collect_dropped (or the host build's twin): {replica: (entries,
+    cmds, read_indexes)} of the replicas listed, ascending — entries as
+    RbeEntry values in the step's append order, cmds their whole Cmds (None
+    when cmds=False), read_indexes the dropped contexts as (low, high).
+    raw=True: the lists themselves as numpy copies of the engine's buffers, a
+    dict with replica, ent_off, entries (ENTRY_DTYPE), cmd_off and cmds (uint8;
+    None when the call returned none), ri_off, read_indexes (CTX_DTYPE)."""
+    o = RbeDroppedList()
+    rc = fn(h, first, count, 0 if cmds else RBE_ENTRIES_NO_CMDS, C.byref(o))
+    if rc != 0:
+        e = EngineError(f"{what} failed with rc={rc}")
+        e.rc = rc
+        raise e
+
+    def arr(ptr, n, dtype):
+        if n == 0 or not ptr:
+            return np.zeros(0, dtype=dtype)
+        b = C.string_at(C.cast(ptr, C.c_void_p), n * np.dtype(dtype).itemsize)
+        return np.frombuffer(b, dtype=dtype).copy()
+
+    d = dict(replica=arr(o.replica, o.n, np.uint64), ent_off=arr(o.ent_off, o.n + 1, np.uint64),
+             entries=arr(o.entries, o.n_entries, ENTRY_DTYPE),
+             cmd_off=arr(o.cmd_off, o.n_entries + 1, np.uint64) if o.cmd_off else None,
+             cmds=arr(o.cmds, o.cmd_bytes, np.uint8) if o.cmd_off else None,
+             ri_off=arr(o.ri_off, o.n + 1, np.uint64),
+             read_indexes=arr(o.read_indexes, o.n_read_indexes, CTX_DTYPE))
+    if raw:
+        return d
+    eraw, coff = d["entries"].tobytes(), d["cmd_off"]
+    braw = d["cmds"].tobytes() if coff is not None else b""
+    es, res = C.sizeof(RbeEntry), {}
+    for i, r in enumerate(d["replica"]):
+        a, b = int(d["ent_off"][i]), int(d["ent_off"][i + 1])
+        en = [RbeEntry.from_buffer_copy(eraw, j * es) for j in range(a, b)]
+        cm = None
+        if coff is not None:
+            cm = [braw[int(coff[j]):int(coff[j]) + en[j - a].cmd_len] for j in range(a, b)]
+        ri = [(int(x["low"]), int(x["high"]))
+              for x in d["read_indexes"][int(d["ri_off"][i]):int(d["ri_off"][i + 1])]]
+        res[int(r)] = (en, cm, ri)
+    return res
+
+
+def dropped_call(fn, h, replica, ent_cap=64, cmd_cap=1 << 16, ctx_cap=16):
+    """rbe_get_dropped (or the host build's twin), sized by the counts it
+    reports: (entries, cmds, read_indexes) in dropped_list_call's shapes."""
+    ents = (RbeEntry * max(1, ent_cap))()
+    ctx = (RbeSystemCtx * max(1, ctx_cap))()
+    cmd = C.create_string_buffer(max(1, cmd_cap))
+    ne, nx, nc = C.c_uint32(), C.c_uint32(), C.c_uint64()
+    rc = fn(h, replica, ents, ent_cap, C.byref(ne), cmd, cmd_cap, C.byref(nc), ctx, ctx_cap,
+            C.byref(nx))
+    if rc != 0:
+        e = EngineError(f"rbe_get_dropped failed with rc={rc}")
+        e.rc = rc
+        raise e
+    if ne.value > ent_cap or nc.value > cmd_cap or nx.value > ctx_cap:
+        return dropped_call(fn, h, replica, max(ent_cap, ne.value), max(cmd_cap, nc.value),
+                            max(ctx_cap, nx.value))
+    es = [ents[i] for i in range(ne.value)]
+    raw, cmds, off = cmd.raw, [], 0
+    for x in es:
+        cmds.append(raw[off:off + x.cmd_len])
+        off += x.cmd_len
+    return es, cmds, [(ctx[i].low, ctx[i].high) for i in range(nx.value)]
 
 
 def push_messages_call(fn, h, groups, msgs, ents, cmds=None):
@@ -1133,6 +1221,21 @@ class Engine(NodeInputs):
         count = self.n_rep - first if count is None else count
         return outbox_list_call(self.lib.rbe_collect_outbox, "rbe_collect_outbox", self.h, first,
                                 count, remote_only, dst_rank, cmds, raw)
+
+    def collect_dropped(self, first: int = 0, count: Optional[int] = None, cmds: bool = True,
+                        raw: bool = False):
+        """rbe_collect_dropped (cfg.drop_lists): the last round's
+        Update.DroppedEntries and DroppedReadIndexes of replicas [first, first +
+        count), gathered on the device in one call: {replica: (entries, cmds,
+        read_indexes)} (dropped_list_call)."""
+        count = self.n_rep - first if count is None else count
+        return dropped_list_call(self.lib.rbe_collect_dropped, "rbe_collect_dropped", self.h,
+                                 first, count, cmds, raw)
+
+    def get_dropped(self, replica: int):
+        """rbe_get_dropped: one replica's (entries, cmds, read_indexes) through
+        plain copies, the independent path collect_dropped is checked against."""
+        return dropped_call(self.lib.rbe_get_dropped, self.h, replica)
 
     def push_messages(self, groups, msgs, ents, cmds=None):
         """Deliver one round's inbound batch from remote senders (rbe_push_messages);

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define RBE_ABI_VERSION 10
+#define RBE_ABI_VERSION 11
 
 /* error codes */
 #define RBE_OK 0
@@ -216,6 +216,15 @@ typedef struct rbe_config {
    * back.  Not with rep_world > 1.  RBE_FAULT_NOMEM remains when both tiers
    * are full (rbe_cold_tier_stats). */
   uint64_t host_pool_bytes;
+  /* Since ABI 11.  Non-zero: the general step keeps each step's
+   * Update.DroppedEntries (a copy of every dropped proposal entry, in the
+   * order the reference appends them, raft.go:1984, 1988) in the round spill
+   * heap, for rbe_collect_dropped / rbe_get_dropped; 16 B per replica more
+   * (rbe_footprint counts them).  0: nothing the engine does changes, and both
+   * calls return RBE_E_STATE.  A step whose list the spill heap has no room
+   * for raises RBE_FAULT_NOMEM and lists no entries. */
+  uint32_t drop_lists;
+  uint32_t pad;
 } rbe_config;
 
 /* Snapshot of one replica (tests, debugging, rbe_get_views). */
@@ -997,6 +1006,80 @@ typedef struct rbe_outbox_list {
 } rbe_outbox_list;
 int rbe_collect_outbox(rbe_engine* e, uint64_t first, uint64_t count, uint32_t flags,
                        int32_t dst_rank, rbe_outbox_list* out);
+
+/* Update.DroppedEntries and Update.DroppedReadIndexes (peer.go:351-356): what
+ * a node completes as dropped after each step (node.go:925-941 — proposals
+ * through pendingProposals.dropped(ClientID, SeriesID, Key), config changes
+ * through pendingConfigChange.dropped(Key), reads through
+ * pendingReadIndexes.dropped(ctx)).  Both calls need cfg.drop_lists
+ * (RBE_E_STATE without).
+ *
+ * rbe_collect_dropped: the lists of the last round of every replica in
+ * [first, first + count), gathered on the device — a lane per replica counts
+ * and writes the offsets, a lane per entry writes the records, a lane per
+ * context the contexts, 16 B per access for the Cmds — and copied into
+ * engine-owned pinned buffers with a fixed number of launches, copies and
+ * waits, whatever is listed.
+ *   Replicas: those of the range this engine steps whose last Update (the
+ *     rule of rbe_collect_entries) has at least one dropped entry or
+ *     ReadIndex, ascending; a replica another rank steps is not listed, and
+ *     with rep_compact the indexes are the local ones.
+ *   Entries: replica[i] owns entries[ent_off[i] .. ent_off[i + 1]) in the
+ *     step's append order.  Index is 0 (a dropped proposal has none), Term the
+ *     term the proposal carried, Type, cmd_len, the first 16 Cmd bytes and the
+ *     session fields as rbe_get_entries fills them.  A ConfigChange proposed
+ *     while another is pending comes back as the ConfigChange entry itself,
+ *     not as the empty entry the log took in its place.
+ *   ReadIndexes: replica[i] owns read_indexes[ri_off[i] .. ri_off[i + 1]) in
+ *     the step's order, the reference's double append for a candidate
+ *     (raft.go:1935-1940) included.
+ *   Cmds: laid out as rbe_entry_list's (cmd_off multiples of 16, pad bytes
+ *     zero).  RBE_ENTRIES_NO_CMDS, the only flag, returns the records only
+ *     (cmd_off and cmds null).  Any other bit is RBE_E_INVALID.
+ * A dropped entry's heap record is in no log, and a forwarded Propose's is in
+ * no outbox and older than the last flush's batch once its leader has dropped
+ * it, so nothing keeps the payload heap from lapping it: read the list before
+ * staging pushes large enough to go round the heap (pushes are accepted; they
+ * are not refused for its sake).  A lapped record makes the whole call RBE_E_STATE with
+ * *out zeroed (records are judged by the host's heap head; those still staged
+ * are uploaded first, as rbe_collect_entries does), and so does a list whose
+ * block does not lie inside the spill heap.  Null e or out, count == 0 or a
+ * range past the engine's replicas is RBE_E_INVALID.  Before the first step
+ * the lists are empty (RBE_OK).  Dropped entries are not part of a group
+ * snapshot: after rbe_import_groups, rbe_launch or rbe_replace_node the
+ * replicas concerned list no dropped entries until their next step (a list's
+ * block is named by a 32-bit granule; the round spill heap, at most 2^32 - 16
+ * granules, never exceeds that), while
+ * their dropped ReadIndexes, which the snapshot's planes carry, are listed as
+ * usual.  A replica with RBE_FAULT_NOMEM may list fewer entries than its
+ * Update counts.  The buffers are a set of their own: a list stays valid until
+ * the next rbe_collect_dropped, the next rbe_step / rbe_run, or rbe_destroy.
+ * The call runs on the engine's stream and may come between
+ * rbe_collect_step_begin and _end.
+ *
+ * rbe_get_dropped: one replica's lists through plain copies (debugging and
+ * cross-checks).  Counts beyond a capacity are reported in *n_ents / *n_ctx /
+ * *cmd_bytes and not written; Cmds are packed back to back, as in
+ * rbe_get_outbox.  Null e, n_ents or n_ctx, or a replica out of range, is
+ * RBE_E_INVALID. */
+typedef struct rbe_system_ctx { uint64_t low, high; } rbe_system_ctx; /* pb.SystemCtx */
+typedef struct rbe_dropped_list {
+  uint64_t first, count;        /* the replica range asked for */
+  uint64_t n;                   /* replicas listed: at least one dropped entry or ReadIndex */
+  uint64_t n_entries, n_read_indexes, cmd_bytes;
+  const uint64_t* replica;      /* n, ascending */
+  const uint64_t* ent_off;      /* n + 1 */
+  const rbe_entry* entries;     /* n_entries; Index 0 */
+  const uint64_t* cmd_off;      /* n_entries + 1, multiples of 16; null with RBE_ENTRIES_NO_CMDS */
+  const uint8_t* cmds;          /* cmd_bytes = cmd_off[n_entries]; pad bytes zero */
+  const uint64_t* ri_off;       /* n + 1 */
+  const rbe_system_ctx* read_indexes; /* n_read_indexes */
+} rbe_dropped_list;
+int rbe_collect_dropped(rbe_engine* e, uint64_t first, uint64_t count, uint32_t flags,
+                        rbe_dropped_list* out);
+int rbe_get_dropped(rbe_engine* e, uint64_t replica, rbe_entry* ents, uint32_t ent_cap,
+                    uint32_t* n_ents, uint8_t* cmd, uint64_t cmd_cap, uint64_t* cmd_bytes,
+                    rbe_system_ctx* ctx, uint32_t ctx_cap, uint32_t* n_ctx);
 
 /* Group-range snapshots: the complete protocol state of groups [first, first + count)
  * between two rounds (every replica's raft, remote, readIndex and log-window rows and
